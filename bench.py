@@ -13,7 +13,13 @@ initial/boundary condition (heat3D.cu:408-453).
 
 Launch (the reference: ``mpirun -n P ./heat3D ...``, heat3D.cu:203-205):
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+      A plain run sets up, warms up, times the K steps and prints the JSON
+      line.  --full adds what takes runs of its own after the timed window:
+      the per-rank phase profile (JSON 'phases') and the time-to-converge run
+      (JSON 'time_to_converge').  --dump-outputs writes the field the timed
+      steps left (DIR/field.npy, a fixed seeded sample when it is large) and
+      the convergence state (DIR/state.npy).
       N > 1 without a launcher: this process starts N fresh worker processes
       (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment) before
       touching the GPU, waits for them under a watchdog and exits with the
@@ -55,6 +61,13 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run what the headline figure does not need: the per-rank "
+                         "phase profile (--profile-sweeps) and the time-to-converge run (--converge-eps)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what they computed as DIR/<name>.npy (float64): "
+                         "field.npy, the global field, whole up to 48 MB, else its values at a fixed seeded "
+                         "sample of points; state.npy, [iterations, last residual, residual norm]")
     ap.add_argument("--grid", type=int, default=1024)
     ap.add_argument("--weak-block", type=int, default=0,
                     help="weak scaling: each GPU owns B^3 interior points, global grid = dims*B + 2 "
@@ -79,7 +92,7 @@ def parse_args(argv=None):
     ap.add_argument("--graph-chunk", type=int, default=0,
                     help="iterations per hipGraph (0 = the solver's choice: 32, 96 for the overlapped N > 1 schedule)")
     ap.add_argument("--converge-eps", type=float, default=1e-5,
-                    help="also measure time-to-converge at this EPS (0 disables).  Default: the reference's "
+                    help="--full: also measure time-to-converge at this EPS (0 disables).  Default: the reference's "
                          "tolerance 1e-5 (1024^3 fp64: 186188 iterations, 240 s on one MI355X, 21.5%% off the "
                          "steady state; profiles/converge_1024_r04.md)")
     ap.add_argument("--converge-time-limit", type=float, default=360.0,
@@ -102,7 +115,7 @@ def parse_args(argv=None):
     ap.add_argument("--timeout", type=float, default=1500.0,
                     help="watchdog (s): a launched job that runs longer is killed and exits non-zero")
     ap.add_argument("--profile-sweeps", type=int, default=8,
-                    help="after the timed window, profile this many more sweeps per rank with timing "
+                    help="--full: after the timed window, profile this many more sweeps per rank with timing "
                          "events at the schedule's phase boundaries (JSON 'phases'; 0 disables)")
     ap.add_argument("--watchdog", type=float, default=300.0,
                     help="native watchdog (s): a rank whose peers stop making progress aborts its communicators")
@@ -189,6 +202,42 @@ def launch(args, argv) -> int:
 
 # ---------------------------------------------------------------------------
 # one rank
+
+DUMP_FIELD_BYTES = 48 << 20  # field.npy: the whole field up to here, else this many bytes of samples
+DUMP_SEED = 20240229
+
+
+def dump_outputs(outdir, solver, state):
+    """--dump-outputs: what the timed steps computed, as float64 .npy files.
+
+    field.npy   the global field after the last timed step (HeatSolver.gather):
+                the whole (N0, N1, N2) array when it fits DUMP_FIELD_BYTES,
+                else its values at DUMP_FIELD_BYTES / 8 flat indices drawn
+                once from a generator seeded with DUMP_SEED (the same points
+                for the same grid in every run and every build)
+    state.npy   [iterations, last residual, residual norm] of the convergence
+                state (HeatSolver.state)
+
+    The initial and boundary condition is analytic and the update is
+    deterministic, so two runs with the same arguments write the same bytes.
+    Every rank calls this (the gather is collective); rank 0 writes."""
+    import numpy as np
+
+    field = solver.gather()
+    if field is None:
+        return None
+    os.makedirs(outdir, exist_ok=True)
+    sampled = field.nbytes > DUMP_FIELD_BYTES
+    if sampled:
+        idx = np.random.default_rng(DUMP_SEED).integers(0, field.size, DUMP_FIELD_BYTES // 8)
+        idx.sort()
+        field = field.reshape(-1)[idx]
+    np.save(os.path.join(outdir, "field.npy"), np.ascontiguousarray(field, dtype=np.float64))
+    np.save(os.path.join(outdir, "state.npy"),
+            np.array([state["iter"], state["last_residual"], state["norm"]], dtype=np.float64))
+    return {"dir": outdir, "files": ["field.npy", "state.npy"], "field_sampled": bool(sampled),
+            "field_values": int(field.size)}
+
 
 def run_rank(args) -> int:
     # one HIP runtime per process, /opt/rocm's: never import torch here
@@ -354,6 +403,7 @@ def run_rank(args) -> int:
     st = s.state()
     # every issued iteration must have been checked and none skipped
     assert st["iter"] == warm + args.steps and st["done"] == 0, st
+    dumped = dump_outputs(args.dump_outputs, s, st) if args.dump_outputs else None
     points = s.interior_points
     value = points * args.steps / dt / 1e9
     esize = 8 if args.dtype == "fp64" else 4
@@ -385,14 +435,14 @@ def run_rank(args) -> int:
     # (interior / halo / boundary / all-reduce / check, compute-stream idle,
     # how much of the halo + boundary chain ran under the interior)
     prof = {}
-    if args.profile_sweeps > 0:
+    if args.full and args.profile_sweeps > 0:
         prof = {k: (round(v, 4) if isinstance(v, float) else v)
                 for k, v in s.native.profile_sweeps(args.profile_sweeps).items()}
     phases = all_gather_objects(dict(rank=rank, **prof), group)
     del s
 
     ttc = None
-    if args.converge_eps and args.converge_eps > 0:
+    if args.full and args.converge_eps and args.converge_eps > 0:
         c = make(args.converge_eps, 10 ** 7,
                  ["--progress", str(args.progress), "--time-limit", str(args.converge_time_limit)]
                  + (["--verbose", str(args.verbose)] if args.verbose > 0 else []))
@@ -457,7 +507,10 @@ def run_rank(args) -> int:
         # traffic is 19.1 B per point per 3 steps (profiles/pmc_tl3_nt_r02.md)
         "temporal_roofline_glups_per_gpu": round(5.6e12 / (2 * esize / max(1, K)) / 1e9, 1),
         "vs_temporal_roofline": round(value / world / (5.6e12 / (2 * esize / max(1, K)) / 1e9), 4),
+        # --full only: the time-to-converge run, and the sweep profile in 'phases'
+        "full": args.full,
         "time_to_converge": ttc,
+        "dumped_outputs": dumped,
         # the HIP runtime / RCCL the ranks ran on (rank 0; every rank's files in placement)
         "runtime": dict(runtime, torch_loaded="torch" in sys.modules),
         "phases": phases,

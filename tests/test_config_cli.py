@@ -1,4 +1,5 @@
 """CLI contract (reference heat3D.cu:270-315, 1078-1106)."""
+import gzip
 import json
 import os
 
@@ -7,7 +8,8 @@ import pytest
 
 from conftest import ROOT, free_port, run_cli
 
-REF_OUT = "/root/reference/HeatEquation3D/output/out.dat"
+# the reference's shipped output artifact (HeatEquation3D/output/out.dat, 27^3), gzipped
+REF_OUT = os.path.join(ROOT, "tests", "golden", "reference_out.dat.gz")
 
 
 def test_config_parse(ext):
@@ -53,7 +55,7 @@ def test_converged_report_and_output(heat3d_bin, tmp_path):
     assert "Simulation has converged in 2513 iterations with a convergence threshold of 1.000000e-05" in r.stdout
     assert "L2-norm error: 0.0192 %" in r.stdout
     out = (tmp_path / "output" / "out.dat").read_text().split("\n")
-    ref = open(REF_OUT).read().split("\n")
+    ref = gzip.open(REF_OUT, "rt").read().split("\n")
     assert out[:3] == ref[:3]  # header byte-compatible with the shipped artifact
     assert len(out) == len(ref)
     # coordinate columns identical to the reference artifact (T differs: its run was broken)

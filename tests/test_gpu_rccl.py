@@ -63,7 +63,7 @@ def test_bench_self_launch_rccl(gpu, tmp_path):
     out = tmp_path / "b.json"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "rccl",
                         "--rccl-host-split", "--grid", "96", "--steps", "6", "--warmup", "3",
-                        "--converge-eps", "0", "--timeout", "100", "--json-out", str(out)],
+                        "--full", "--converge-eps", "0", "--timeout", "100", "--json-out", str(out)],
                        capture_output=True, text=True, timeout=110, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert p.returncode == 0, p.stderr[-3000:]
@@ -96,7 +96,7 @@ def test_bench_under_torchrun_rccl(gpu, tmp_path):
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
                         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--comm", "rccl", "--rccl-host-split",
-                        "--grid", "96", "--steps", "6", "--warmup", "3", "--converge-eps", "0",
+                        "--grid", "96", "--steps", "6", "--warmup", "3", "--full", "--converge-eps", "0",
                         "--json-out", str(out)],
                        capture_output=True, text=True, timeout=150, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})

@@ -82,10 +82,12 @@ def main():
         if c == 1:
             row = config1(a.steps)
         elif c == 2:
-            b = run_bench(["--grid", "512", "--steps", str(4 * a.steps), "--converge-eps", "1e-3"], 1, a.timeout)
+            b = run_bench(["--grid", "512", "--steps", str(4 * a.steps), "--full", "--converge-eps", "1e-3"],
+                          1, a.timeout)
             row = {"config": 2, "name": "512^3 fp64 1 GPU", "mode": "measured", "bench": b}
         elif c == 3:
-            extra = ["--grid", "1024", "--decomp", "8x1x1", "--steps", str(a.steps), "--converge-eps", "1e-3"]
+            extra = ["--grid", "1024", "--decomp", "8x1x1", "--steps", str(a.steps), "--full",
+                     "--converge-eps", "1e-3"]
             if real:
                 row = {"config": 3, "name": "1024^3 fp64 8 GPUs slab", "mode": "measured",
                        "bench": run_bench(extra, 8, a.timeout)}

@@ -5,7 +5,7 @@ Used to attribute the drop from the bench's 20-step window rate to the rate
 sustained over the ~4-minute time-to-converge run: the
 samples show whether the shader clock falls as the run goes on.
 
-  python tools/clock_sampler.py --every 10 --out gpurun_out/x/clocks.jsonl -- python bench.py ...
+  python tools/clock_sampler.py --every 10 --out clocks.jsonl -- python bench.py --full ...
 
 The command runs as a child process (never exec'd into); this script exits
 with the child's exit code.  Each sample is one JSON line: seconds since the

@@ -12,8 +12,8 @@
 #                                                                          -> OUT/build.log
 #   suite [PYTEST ARGS]     python -m pytest -m gpu (default: tests/)       -> OUT/pytest.log
 #   smoke                   __graft_entry__.smoke()                        -> OUT/smoke.log
-#   bench [BENCH ARGS]      python bench.py ARGS (1 GPU, or --gpus N self-launch)
-#                                                                          -> OUT/bench<i>.json
+#   bench [BENCH ARGS]      python bench.py ARGS (1 GPU, or --gpus N self-launch; --full among ARGS for
+#                           the phase profile and the time-to-converge run) -> OUT/bench<i>.json
 #   rccl [N] [BENCH ARGS]   N (default 2) ranks of bench.py sharing the one GPU over real RCCL
 #                           (every rank its own NCCL_HOSTID: RCCL's network transport on loopback),
 #                           each rank started by this shell                -> OUT/rccl<i>.json
