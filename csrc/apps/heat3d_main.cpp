@@ -79,7 +79,12 @@ static int run_reference_scheme(const Config& cfg) {
 static int drive(const Config& cfg, Solver& solver) {
   const bool root = solver.is_root();
   if (root && !cfg.quiet) std::cout << cfg.echo_banner() << std::flush;
+  // the source before initialize() (a --restart checkpoint written with a
+  // source needs it, and the start-up timing then runs the source kernels),
+  // the initial field after it
+  if (!cfg.source_file.empty()) solver.set_source_file(cfg.source_file);
   solver.initialize();
+  if (!cfg.initial_file.empty()) solver.set_field_file(cfg.initial_file);
   RunResult r = solver.run();
   double gerr = 0, lerr = 0;
   solver.compute_error(&gerr, &lerr);

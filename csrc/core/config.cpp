@@ -7,6 +7,8 @@
 #include <iomanip>
 #include <sstream>
 
+#include <sys/stat.h>
+
 namespace heat3d {
 
 const char* face_name(Face f) {
@@ -101,6 +103,10 @@ std::string Config::usage() {
      << "                            stop; CPU, all ranks of --decomp / --virtual-ranks in-process)\n"
      << "  --checkpoint-every K --checkpoint-dir DIR   periodic binary checkpoints\n"
      << "  --restart DIR             resume from a checkpoint directory\n"
+     << "  --source FILE             volumetric heat source q (T_t = alpha lap(T) + q): raw little-endian\n"
+     << "                            float64, NX*NY*NZ values, z fastest (the checkpoint field file's order)\n"
+     << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
+     << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
      << "  --verify-halo K           race detection: checksum every halo face every K iterations\n"
      << "  --timers                  per-phase GPU timing (synchronised diagnostic run)\n"
@@ -242,6 +248,8 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--timers") c.timers = true;
     else if (key == "--checkpoint-dir") c.checkpoint_dir = get("--checkpoint-dir");
     else if (key == "--restart") c.restart = get("--restart");
+    else if (key == "--source") c.source_file = get("--source");
+    else if (key == "--initial") c.initial_file = get("--initial");
     else if (key == "--json-out") c.json_out = get("--json-out");
     else if (key == "--verbose") c.verbose = (int)to_i64(get("--verbose"), "--verbose");
     else if (key == "--progress") c.progress_s = to_f64(get("--progress"), "--progress");
@@ -344,6 +352,20 @@ Config Config::parse(int argc, const char* const* argv) {
   if (c.watchdog_s <= 0) throw UsageError("--watchdog must be > 0");
   if (c.progress_s < 0) throw UsageError("--progress must be >= 0");
   if (c.time_limit_s < 0) throw UsageError("--time-limit must be >= 0");
+  // --source / --initial: NX*NY*NZ float64 values; a wrong size is a usage error
+  for (const auto* f : {&c.source_file, &c.initial_file}) {
+    if (f->empty()) continue;
+    const char* flag = f == &c.source_file ? "--source" : "--initial";
+    struct stat st {};
+    if (::stat(f->c_str(), &st) != 0) throw UsageError(std::string(flag) + ": cannot read file " + *f);
+    const long long want = (long long)c.n[0] * c.n[1] * c.n[2] * 8;
+    if ((long long)st.st_size != want)
+      throw UsageError(std::string(flag) + " file " + *f + " has " + std::to_string((long long)st.st_size) +
+                       " bytes, expected " + std::to_string(want) + " (NX*NY*NZ little-endian float64 values)");
+  }
+  if (!c.initial_file.empty() && !c.restart.empty()) throw UsageError("--initial and --restart are exclusive");
+  if ((!c.source_file.empty() || !c.initial_file.empty()) && c.scheme == "reference")
+    throw UsageError("--source / --initial are not part of --scheme reference");
   return c;
 }
 

@@ -65,6 +65,8 @@ struct Config {
   bool timers = false;                    // per-phase timing (synchronised diagnostic run)
   std::string checkpoint_dir;
   std::string restart;
+  std::string source_file;   // --source: heat source q, raw float64 NX*NY*NZ
+  std::string initial_file;  // --initial: initial field with its wall values, same format
   std::string json_out;
   int verbose = 0;
   double progress_s = 0;          // run(): stderr heartbeat period (0 = off)

@@ -15,15 +15,19 @@ namespace heat3d {
 namespace cpu {
 namespace H3D_ROWS_NS {
 
-template <typename Real>
-static inline double row(const Real* __restrict in, Real* __restrict out, int64_t n, int64_t sx, int64_t sy,
-                         Real Dx, Real Dy, Real Dz) {
+template <typename Real, bool SRC>
+static inline double row(const Real* __restrict in, Real* __restrict out, const Real* __restrict src, int64_t n,
+                         int64_t sx, int64_t sy, Real Dx, Real Dy, Real Dz) {
   double lres = 0.0;
   bool nan = false;
   for (int64_t k = 0; k < n; ++k) {
     const Real T = in[k];
-    const Real nv = ftcs_update<Real>(T, in[k - sx], in[k + sx], in[k - sy], in[k + sy], in[k - 1], in[k + 1], Dx,
-                                      Dy, Dz);
+    Real nv;
+    if constexpr (SRC)
+      nv = ftcs_update_src<Real>(T, in[k - sx], in[k + sx], in[k - sy], in[k + sy], in[k - 1], in[k + 1], Dx, Dy,
+                                 Dz, src[k]);
+    else
+      nv = ftcs_update<Real>(T, in[k - sx], in[k + sx], in[k - sy], in[k + sy], in[k - 1], in[k + 1], Dx, Dy, Dz);
     out[k] = nv;
     const double d = resid_abs(nv, T);  // in the field's precision (kernels.hpp)
     nan |= d != d;
@@ -34,10 +38,18 @@ static inline double row(const Real* __restrict in, Real* __restrict out, int64_
 
 double ftcs_row_f64(const double* in, double* out, int64_t n, int64_t sx, int64_t sy, double Dx, double Dy,
                     double Dz) {
-  return row<double>(in, out, n, sx, sy, Dx, Dy, Dz);
+  return row<double, false>(in, out, nullptr, n, sx, sy, Dx, Dy, Dz);
 }
 double ftcs_row_f32(const float* in, float* out, int64_t n, int64_t sx, int64_t sy, float Dx, float Dy, float Dz) {
-  return row<float>(in, out, n, sx, sy, Dx, Dy, Dz);
+  return row<float, false>(in, out, nullptr, n, sx, sy, Dx, Dy, Dz);
+}
+double ftcs_row_src_f64(const double* in, double* out, const double* src, int64_t n, int64_t sx, int64_t sy,
+                        double Dx, double Dy, double Dz) {
+  return row<double, true>(in, out, src, n, sx, sy, Dx, Dy, Dz);
+}
+double ftcs_row_src_f32(const float* in, float* out, const float* src, int64_t n, int64_t sx, int64_t sy, float Dx,
+                        float Dy, float Dz) {
+  return row<float, true>(in, out, src, n, sx, sy, Dx, Dy, Dz);
 }
 
 }  // namespace H3D_ROWS_NS
@@ -47,8 +59,10 @@ const RowKernels& cpu_row_kernels() {
   static const RowKernels k = [] {
     __builtin_cpu_init();
     if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"))
-      return RowKernels{rows_fma::ftcs_row_f64, rows_fma::ftcs_row_f32, "x86-64+fma+avx2"};
-    return RowKernels{rows_generic::ftcs_row_f64, rows_generic::ftcs_row_f32, "x86-64 (libm fma)"};
+      return RowKernels{rows_fma::ftcs_row_f64, rows_fma::ftcs_row_f32, "x86-64+fma+avx2", rows_fma::ftcs_row_src_f64,
+                        rows_fma::ftcs_row_src_f32};
+    return RowKernels{rows_generic::ftcs_row_f64, rows_generic::ftcs_row_f32, "x86-64 (libm fma)",
+                      rows_generic::ftcs_row_src_f64, rows_generic::ftcs_row_src_f32};
   }();
   return k;
 }

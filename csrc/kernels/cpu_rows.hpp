@@ -20,10 +20,17 @@ template <typename Real>
 using FtcsRowFn = double (*)(const Real* in, Real* out, int64_t n, int64_t sx, int64_t sy, Real Dx, Real Dy,
                              Real Dz);
 
+// the same with a heat source: out[k] = ftcs_update_src(in[k], ..., src[k])
+template <typename Real>
+using FtcsRowSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t sx, int64_t sy,
+                                Real Dx, Real Dy, Real Dz);
+
 struct RowKernels {
   FtcsRowFn<double> f64;
   FtcsRowFn<float> f32;
   const char* isa;
+  FtcsRowSrcFn<double> src_f64;
+  FtcsRowSrcFn<float> src_f32;
 };
 
 const RowKernels& cpu_row_kernels();
@@ -31,10 +38,14 @@ const RowKernels& cpu_row_kernels();
 namespace rows_generic {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
 double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
+double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
+double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
 }  // namespace rows_generic
 namespace rows_fma {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
 double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
+double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
+double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
 }  // namespace rows_fma
 
 }  // namespace cpu

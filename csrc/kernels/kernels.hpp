@@ -73,6 +73,10 @@ struct StencilParams {
   // after it, which cost ~10 us per sweep on the critical path (a one-lane
   // kernel and its dispatch; profiles/r06)
   bool fuse_check = false;
+  // volumetric heat source S = dtype(dt * q): a field in the same Layout as
+  // in/out (ghost shells included), added to every updated point
+  // (ftcs_update_src).  nullptr: no source, the kernels without a source term.
+  const void* src = nullptr;
 };
 
 struct InitParams {
@@ -135,7 +139,8 @@ bool lean_pair_supported(DType t, const KernelSpec& k);
 // z tile stride of the pair kernel for a box (host-side choice, stencil_tbp.hip)
 int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, int U, int L, int esize);
 // Is the lean kernel variant that k resolves to for dtype t instantiated?
-bool lean_supported(DType t, const KernelSpec& k);
+// with_source: its heat-source form (StencilParams::src != nullptr)
+bool lean_supported(DType t, const KernelSpec& k, bool with_source = false);
 // Any multi-step kind -> its kernel
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 void pack_box(DType t, const void* f, const Layout& L, const Box& b, void* buf, void* stream);
@@ -226,6 +231,21 @@ H3D_HD inline Real ftcs_update(Real c, Real xm, Real xp, Real ym, Real yp, Real 
   const Real ay = h3d_fma(Real(-2), c, yp) + ym;
   const Real az = h3d_fma(Real(-2), c, zp) + zm;
   return h3d_fma(Dz, az, h3d_fma(Dy, ay, h3d_fma(Dx, ax, c)));
+}
+
+// FTCS update with a volumetric heat source, T_t = alpha lap(T) + q:
+//   T' = ftcs_update(...) + S,  S = dtype(dt * q) rounded once when the source
+// is set.  The add is a separate, rounded operation, never contracted into
+// the update's last fused multiply-add (every unit is built with
+// -ffp-contract=off, as the plain adds inside ftcs_update require too).
+template <typename Real>
+H3D_HD inline Real add_source(Real u, Real S) {
+  return u + S;
+}
+template <typename Real>
+H3D_HD inline Real ftcs_update_src(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real Dx,
+                                   Real Dy, Real Dz, Real S) {
+  return add_source<Real>(ftcs_update<Real>(c, xm, xp, ym, yp, zm, zp, Dx, Dy, Dz), S);
 }
 
 // Residual term of one point, |T^{n+1} - T^n|, taken in the field's

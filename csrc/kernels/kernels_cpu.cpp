@@ -74,13 +74,20 @@ static void stencil_t(const StencilParams& p) {
     if constexpr (sizeof(Real) == 8) return cpu_row_kernels().f64;
     else return cpu_row_kernels().f32;
   }();
+  const auto rowsrc = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().src_f64;
+    else return cpu_row_kernels().src_f32;
+  }();
+  const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
   const int64_t nk = b.extent(2);
 #pragma omp parallel for collapse(2) schedule(static) reduction(max : resbits) if (omp_worth(b.volume()))
   for (int64_t i = b.lo[0]; i < b.hi[0]; ++i)
     for (int64_t j = b.lo[1]; j < b.hi[1]; ++j) {
       const int64_t c = L.index(i, j, b.lo[2]);
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
-      const double lres = nk > 0 ? rowfn(in + c, out + c, nk, sx, sy, Dx, Dy, Dz) : 0.0;
+      const double lres = nk <= 0 ? 0.0
+                          : src   ? rowsrc(in + c, out + c, src + c, nk, sx, sy, Dx, Dy, Dz)
+                                  : rowfn(in + c, out + c, nk, sx, sy, Dx, Dy, Dz);
       unsigned long long bits;
       std::memcpy(&bits, &lres, sizeof(bits));
       resbits = bits > resbits ? bits : resbits;

@@ -17,6 +17,10 @@ namespace hip {
   extern template void launch_tbl<T, R, WY, K, Q, N, S>(const StencilParams&, const KernelSpec&, hipStream_t);
 #include "stencil_tbl_variants.inc"
 #undef H3D_V
+#define H3D_VS(T, R, WY, K, Q, N, S, P) \
+  extern template void launch_tbl<T, R, WY, K, Q, N, S, true>(const StencilParams&, const KernelSpec&, hipStream_t);
+#include "stencil_tbl_src_variants.inc"
+#undef H3D_VS
 
 // Tile stride along z.  64 - 2K stored columns per 64-lane tile, or — fp64
 // only — the largest multiple of 8 below it, which starts every tile's stored
@@ -58,6 +62,52 @@ static int lean_z_stride_plan(int64_t nx, int64_t ny, int64_t nz, int K, int esi
   };
   constexpr double kAlignedGain = 0.92;
   return cost(aligned) * kAlignedGain < cost(wide) ? aligned : wide;
+}
+
+// Heat-source forms (stencil_tbl_src_variants.inc).  With a source the default
+// form is the one-value-per-lane lean kernel for fp32 too (the pair kernel,
+// stencil_tbp.hip, has no source form): an unset V resolves to 1.
+// p == nullptr: only report whether the source form of k exists.
+template <typename Real>
+static bool dispatch_tbl_src(const StencilParams* p, const KernelSpec& k, hipStream_t s) {
+  constexpr bool f64 = sizeof(Real) == 8;
+  KernelSpec k1 = k;
+  if (k1.V == 0) k1.V = 1;
+  const KernelSpec r = k1.resolved(f64 ? DType::F64 : DType::F32);
+  const int K = k.K, R = r.R, WY = r.WY, Q = r.NT;
+  if (p) {
+    // the thin x slabs' y-marching tiles, chosen as dispatch_tbl chooses them
+    const Box& bx = p->box;
+    const bool dflt = k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0;
+    if (K == 3 && dflt && bx.extent(0) == 4 && bx.extent(1) >= 16 * bx.extent(0)) {
+      launch_tbl<Real, 2, 5, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+      return true;
+    }
+    if (K == 3 && dflt && bx.extent(0) > 0 && bx.extent(0) <= 2 * K && bx.extent(1) >= 16 * bx.extent(0)) {
+      launch_tbl<Real, 3, 3, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+      return true;
+    }
+    if (K == 4 && dflt && bx.extent(0) > 0 && bx.extent(0) <= K && bx.extent(1) >= 16 * bx.extent(0)) {
+      launch_tbl<Real, 3, 4, 4, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+      return true;
+    }
+  }
+  if (r.V != 1 || r.WZ != 1 || Q != 3) return false;
+  const int O = r.O > 0 ? r.O : 0;
+#define H3D_TBLS(RR, YY, KK, AA)                                      \
+  if (R == RR && WY == YY && K == KK && O == (AA)) {                  \
+    if (p) launch_tbl<Real, RR, YY, KK, 3, (AA), false, true>(*p, k, s); \
+    return true;                                                      \
+  }
+  if constexpr (f64) {
+    H3D_TBLS(3, 16, 3, 2) H3D_TBLS(3, 16, 3, 2 | kResidualLastOnly)
+    H3D_TBLS(3, 12, 4, 2) H3D_TBLS(3, 12, 4, 2 | kResidualLastOnly)
+    H3D_TBLS(5, 16, 2, 2) H3D_TBLS(5, 16, 2, 2 | kResidualLastOnly)
+  } else {
+    H3D_TBLS(3, 16, 3, 0) H3D_TBLS(4, 16, 4, 0) H3D_TBLS(3, 16, 2, 0)
+  }
+#undef H3D_TBLS
+  return false;
 }
 
 // p == nullptr: only report whether the variant k resolves to exists
@@ -147,12 +197,25 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   return false;
 }
 
-bool lean_supported(DType t, const KernelSpec& k) {
+bool lean_supported(DType t, const KernelSpec& k, bool with_source) {
+  if (with_source)
+    return t == DType::F64 ? dispatch_tbl_src<double>(nullptr, k, nullptr) : dispatch_tbl_src<float>(nullptr, k, nullptr);
   return t == DType::F64 ? dispatch_tbl<double>(nullptr, k, nullptr) : dispatch_tbl<float>(nullptr, k, nullptr);
 }
 
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   if (p.box.empty()) return;
+  if (p.src) {
+    const bool ok =
+        t == DType::F64 ? dispatch_tbl_src<double>(&p, k, S(stream)) : dispatch_tbl_src<float>(&p, k, S(stream));
+    if (!ok) {
+      const KernelSpec r = k.resolved(t);
+      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t)
+                                        << ") has no heat-source form; with a source use the default --kernel2 "
+                                           "(tl2, tl3 or tl4 without shape fields)");
+    }
+    return;
+  }
   const bool ok = t == DType::F64 ? dispatch_tbl<double>(&p, k, S(stream)) : dispatch_tbl<float>(&p, k, S(stream));
   if (!ok) {
     const KernelSpec r = k.resolved(t);

@@ -1,0 +1,287 @@
+// heat3d-mi355x — the lean K-step sweep kernel's definition, included by
+// stencil_tbl_impl.hpp once per form: H3D_TBL_NAME stencil_tbl with
+// H3D_TBL_SRC 0, and stencil_tbl_src with H3D_TBL_SRC 1 (heat source, see the
+// comment there).  Textual inclusion keeps the kernel without a source exactly
+// the code it was before the source form existed.
+template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false>
+__global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__ in, Real* __restrict__ out,
+#if H3D_TBL_SRC
+                                                       const Real* __restrict__ src,
+#endif
+                                                       TBLArgs g, Real Dx, Real Dy, Real Dz,
+                                                       unsigned long long* res, const int* done) {
+  static_assert(K >= 2 && K <= 6, "temporal depth");
+  // T^n ring: Q = 3 loads plane x+2 into the slot stage 0 frees at step x
+  // ((K-1)/K of a step of latency cover); Q >= 4 loads plane x+Q-2 at the
+  // start of step x (Q-3 steps of cover)
+  static_assert(Q == 3 || Q == 4 || Q == 6, "T^n ring size");
+  constexpr int TY = WY * R;
+  constexpr int YS = TY - 2 * K;   // tile stride along y (stored rows)
+  // x-loop unroll making every ring index and the LDS parity static
+  constexpr int U = lcm_l(lcm_l(Q, 3), 2);
+  static_assert(YS > 0 && R <= 16, "tile too small for depth K");
+  // NTS bit kResidualLastOnly: only the last step's residual (monotone check)
+  constexpr bool RL = (NTS & kResidualLastOnly) != 0;
+  constexpr int ST = NTS & ~kResidualLastOnly;  // the stores' cache-policy bits
+  __shared__ __attribute__((aligned(16))) Real s_row[2][K][WY][2][64];
+  static_assert(sizeof(s_row) >= WY * K * sizeof(unsigned long long), "residual scratch");
+  if (flag_set(done)) {
+    if (g.fst) fused_check_tail<K, RL>(g.fst, g.fslot, g.fblocks);
+    return;
+  }
+
+  // piece decode: blocks dealt round-robin over the 8 XCDs; consecutive
+  // pieces (neighbouring tiles) share an XCD's L2 (same encoding as tbr)
+  auto remap = [](int i, int n) {
+    const int c = i & 7;
+    return c * (n >> 3) + min(c, n & 7) + (i >> 3);
+  };
+  const int blk = blockIdx.x;
+  const int zs = g.zs;
+  const int ntile = g.nzb * g.nyb;
+  const int nxb = g.bhi[0] - g.blo[0];
+  // This workgroup's piece: plane steps [w, wend) of the tile-major list
+  // (tile t, plane x) -> t * nxb + x, one piece per block, x segments of
+  // `seg` planes (plan_x: whole rounds of pieces, then a split tail); each
+  // piece pays the 2(K-1)-plane pipeline fill.  (The persistent walk of round 3,
+  // every block a contiguous 1/n of the list, measured 18-22% slower on
+  // MI355X: the x plan's concurrent workgroups sweep neighbouring tiles over
+  // the same x planes, so their overlapping halo rows are L2 hits.)
+  int64_t w, wend;
+  {
+    int pc, part;
+    const int rr = g.rb & 0x3fffffff;
+    if (blk < g.n1) {
+      pc = remap(blk, g.n1);
+      part = 0;
+    } else if (blk < g.n1 + rr) {
+      pc = g.n1 + remap(blk - g.n1, rr);
+      part = 1;
+    } else {
+      pc = g.n1 + remap(blk - g.n1 - rr, rr);
+      part = 2;
+    }
+    const int xs = pc / ntile;
+    const int tt = pc - xs * ntile;
+    const int seg = g.segsplit & 0xffff, split = g.segsplit >> 16;
+    int xlo_p = xs * seg, xhi_p = min(xlo_p + seg, nxb);
+    if (part == 1 && (g.rb >> 30)) xhi_p = min(xhi_p, xlo_p + split);
+    if (part == 2) xlo_p = min(xlo_p + split, xhi_p);
+    w = (int64_t)tt * nxb + xlo_p;
+    wend = (int64_t)tt * nxb + xhi_p;
+  }
+
+  // tile order: z fastest
+  const int tt = (int)(w / nxb);
+  const int xlo_p = (int)(w - (int64_t)tt * nxb);
+  const int xhi_p = (int)min((int64_t)nxb, xlo_p + (wend - w));
+  const int zb = tt % g.nzb, ybk = tt / g.nzb;
+
+  const int wave = sgpr(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int c0 = g.c00 + zb * zs;         // tile's first loaded column
+  const int r0 = g.r00 + ybk * YS;          // tile's first loaded row
+  const int yb = r0 + wave * R;             // this wave's first row
+  const int col = c0 + lane;
+  const int xa = g.blo[0] + xlo_p, xe = g.blo[0] + xhi_p;
+  const int x0 = xa - (K - 1), xlast = xe + K - 2;
+  const int64_t sx = g.sx;
+
+  // ---- uniform (per wave) classification
+  const bool zfast = c0 >= g.uzlo && c0 + 64 <= g.uzhi;
+  const bool wrows = wave * R >= K && wave * R + R <= TY - K && yb >= g.uylo && yb + R <= g.uyhi &&
+                     yb >= g.blo[1] && yb + R <= g.bhi[1];
+  const bool wfast = zfast && wrows;
+  // steps whose every stage is valid, updated, counted and (last stage) stored
+  const int xf_lo = max(max(x0 + 2 * (K - 1), g.ulo + K - 1), g.blo[0] + K - 1);
+  const int xf_hi = min(min(xlast, g.uhi - 1), g.bhi[0] + K - 2);
+
+  // masked form, per row r (uniform, one SGPR): bit r = row in the update
+  // range, bit R + r = stored row, bit 2R + s*R + r = row counted at stage s
+  // (64-bit when the rows x stages outgrow one SGPR: 8-wave tiles of 6 rows)
+  using YMask = std::conditional_t<(2 * R + K * R <= 32), unsigned, unsigned long long>;
+  static_assert(2 * R + K * R <= 64, "row mask bits");
+  YMask ybits = 0;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const int row = yb + r, rp = wave * R + r;
+    if (row >= g.uylo && row < g.uyhi) ybits |= YMask(1) << r;
+    if (rp >= K && rp < TY - K && row >= g.blo[1] && row < g.bhi[1]) ybits |= YMask(1) << (R + r);
+#pragma unroll
+    for (int s = 0; s < K; ++s)
+      if (row >= g.uylo && row < g.uyhi && rp >= s + 1 && rp < TY - s - 1 && row >= g.blo[1] - (K - 1 - s) &&
+          row < g.bhi[1] + (K - 1 - s))
+        ybits |= YMask(1) << (2 * R + s * R + r);
+  }
+  if constexpr (sizeof(YMask) == 4) {
+    ybits = (unsigned)sgpr((int)ybits);
+  } else {
+    ybits = ((YMask)(unsigned)sgpr((int)(ybits >> 32)) << 32) | (unsigned)sgpr((int)(unsigned)ybits);
+  }
+
+  // per-lane masks (constant over the piece)
+  const bool zin = col >= g.uzlo && col < g.uzhi;
+  const bool zst = lane >= K && lane < K + zs && col >= g.blo[2] && col < g.bhi[2];
+
+  // ---- addressing: uniform base of row yb, column c0; clamped row offsets
+  // (uniform by construction: kernel arguments and the readfirstlane'd wave
+  // index; pointers stay in the global address space)
+  // Loads: base at the wave's first clamped row; a buffer soffset is an
+  // unsigned 32-bit value, so every row offset must be >= 0 (clamping is
+  // monotonic: clamp(yb + r) >= clamp(yb)).  Stores only touch stored rows,
+  // which are real rows at or after yb.
+  auto yclamp = [&](int row) { return min(max(row, g.ylo_live), g.yhi_live); };
+  const int ybc = yclamp(yb);
+  const Real* __restrict__ inw = in + (g.origin + (int64_t)ybc * g.sy + c0);
+  Real* __restrict__ outw = out + (g.origin + (int64_t)yb * g.sy + c0);
+#if H3D_TBL_SRC
+  const Real* __restrict__ srcw = src + (g.origin + (int64_t)ybc * g.sy + c0);
+#endif
+  // row byte offsets (clamped rows fold in), 0 <= roff < 2^31: checked in launch_tbl
+  int roff[R];
+#pragma unroll
+  for (int r = 0; r < R; ++r) roff[r] = sgpr((yclamp(yb + r) - ybc) * (int)g.sy * (int)sizeof(Real));
+  const int sy_b = (int)g.sy * (int)sizeof(Real);
+  const unsigned lane_b = (unsigned)lane * (unsigned)sizeof(Real);
+
+  Real q[Q][R];              // T^n ring: plane p in slot (p - x0 + 1) mod Q
+  Real f[K - 1][3][R];       // F_{s+1}(p) in f[s][(p + s) mod 3]
+  Real m[K];                 // per-lane residual maxima (field precision, widened at the end)
+  bool nan_seen = false;
+#pragma unroll
+  for (int s = 0; s < K; ++s) m[s] = Real(0);
+#pragma unroll
+  for (int s = 0; s < K - 1; ++s)
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int r = 0; r < R; ++r) f[s][i][r] = Real(0);
+
+  auto load_plane = [&](int x, Real (&d)[R]) {
+    const int xc = min(max(x, g.xlo_live), g.xhi_live);
+    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(inw + (int64_t)xc * sx);
+#pragma unroll
+    for (int r = 0; r < R; ++r) d[r] = buf_load<Real>(rs, lane_b, roff[r]);
+  };
+  constexpr int NPRE = Q == 3 ? 3 : Q - 1;  // planes resident / in flight before step x0
+#pragma unroll
+  for (int i = 0; i < NPRE; ++i) load_plane(x0 - 1 + i, q[i]);
+
+  // One plane step.  FAST: every condition below is known true.
+  auto step = [&](auto fast_tag, const int x, auto ph_tag) {
+    constexpr bool FAST = decltype(fast_tag)::value;
+    constexpr int ph = decltype(ph_tag)::value;
+    constexpr int sM = ph % Q, sC = (ph + 1) % Q, sP = (ph + 2) % Q;
+    constexpr int fw = ph % 3, fc = (ph + 2) % 3, fm = (ph + 1) % 3;
+    constexpr int par = ph & 1;  // LDS buffer (U is even)
+    if constexpr (Q >= 4) load_plane(x + Q - 2, q[(ph + Q - 1) % Q]);
+    // publish the edge rows of every stage's centre plane
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      const Real(&C)[R] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
+      s_row[par][s][wave][0][lane] = C[0];
+      s_row[par][s][wave][1][lane] = C[R - 1];
+    }
+    __syncthreads();
+    const int wl = max(wave - 1, 0), wh = min(wave + 1, WY - 1);
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      Real(&M)[R] = s == 0 ? q[sM] : f[s > 0 ? s - 1 : 0][fm];
+      Real(&C)[R] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
+      Real(&P)[R] = s == 0 ? q[sP] : f[s > 0 ? s - 1 : 0][fw];
+      const Real lo = s_row[par][s][wl][1][lane];
+      const Real hi = s_row[par][s][wh][0][lane];
+      const int p = x - s;
+#if H3D_TBL_SRC
+      // the source rows of this stage's plane (clamped as load_plane)
+      Real S[R];
+      {
+        const int pc = min(max(p, g.xlo_live), g.xhi_live);
+        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(srcw + (int64_t)pc * sx);
+#pragma unroll
+        for (int r = 0; r < R; ++r) S[r] = buf_load<Real>(rs, lane_b, roff[r]);
+      }
+#endif
+      // masked form: uniform x conditions of this stage
+      bool xin = true, xcnt = true, xst = true;
+      if constexpr (!FAST) {
+        xin = p >= g.ulo && p < g.uhi;
+        xcnt = xin && x >= x0 + 2 * s && x <= xlast && p >= g.blo[0] - (K - 1 - s) && p < g.bhi[0] + (K - 1 - s);
+        xst = p >= xa && p < xe;
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        const Real ym = r == 0 ? lo : C[r > 0 ? r - 1 : 0];
+        const Real yp = r == R - 1 ? hi : C[r + 1 < R ? r + 1 : 0];
+        const Real zm = dpp_shr1z(C[r]);
+        const Real zp = dpp_shl1z(C[r]);
+        // same operation order as kernels.hpp ftcs_update in both frames
+#if H3D_TBL_SRC
+        const Real nv = add_source<Real>(SW ? ftcs<Real>(C[r], ym, yp, M[r], P[r], zm, zp, Dx, Dy, Dz)
+                                            : ftcs<Real>(C[r], M[r], P[r], ym, yp, zm, zp, Dx, Dy, Dz),
+                                         S[r]);
+#else
+        const Real nv = SW ? ftcs<Real>(C[r], ym, yp, M[r], P[r], zm, zp, Dx, Dy, Dz)
+                           : ftcs<Real>(C[r], M[r], P[r], ym, yp, zm, zp, Dx, Dy, Dz);
+#endif
+        const Real d = resid_abs_r(nv, C[r]);
+        bool upd = true, cnt = true, st = true;
+        if constexpr (!FAST) {
+          upd = xin && ((ybits >> r) & 1);
+          cnt = xcnt && ((ybits >> (2 * R + s * R + r)) & 1);
+          st = xst && ((ybits >> (R + r)) & 1);
+        }
+        if (s < K - 1) {
+          Real(&N)[R] = f[s < K - 1 ? s : 0][fw];
+          if constexpr (FAST) N[r] = nv;
+          else N[r] = (upd && zin) ? nv : C[r];
+        }
+        if (!RL || s == K - 1) {
+          if constexpr (FAST) {
+            m[s] = fmax(m[s], d);
+          } else {
+            if (cnt) m[s] = fmax(m[s], d);
+          }
+        }
+        if (s == K - 1 && st) {
+          // T^{n+K} on the stored region (inside the box, hence the update range)
+          nan_seen |= zst && (nv != nv);
+          if (zst) buf_store<Real, ST>(nv, plane_rsrc(outw + (int64_t)p * sx), lane_b, r * sy_b);
+        }
+      }
+      if constexpr (Q == 3) {
+        if (s == 0) load_plane(x + 2, q[sM]);  // the slot stage 0 has just freed
+      }
+    }
+  };
+
+  // whole chunks of U steps (the unrolled body needs a constant trip count);
+  // padded steps past xlast take the masked form and count / store nothing
+  for (int xb = x0; xb <= xlast; xb += U) {
+    static_for<0, U>([&](auto ph_tag) {
+      constexpr int ph = decltype(ph_tag)::value;
+      const int x = xb + ph;
+      if (wfast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag);
+      else step(std::false_type{}, x, ph_tag);
+    });
+  }
+
+  // this piece's residuals (the lane masks depend on its tile)
+  if (res) {
+    double mm[K];
+#pragma unroll
+    for (int s = 0; s < K; ++s) {
+      // stage s counts lanes inside its cone, the update range and the box
+      // widened by K-1-s (deep-halo points still in flight stay excluded)
+      const bool ok = zin && lane >= s + 1 && lane < 63 - s && col >= g.blo[2] - (K - 1 - s) &&
+                      col < g.bhi[2] + (K - 1 - s);
+      mm[s] = ok ? (double)m[s] : 0.0;
+    }
+    // the row exchange buffer is dead: reuse it for the per-wave maxima
+    __syncthreads();
+    residual_commit_block<WY, K>(res, mm, nan_seen,
+                                 *reinterpret_cast<unsigned long long(*)[WY][K]>(&s_row[0][0][0][0][0]));
+  }
+  if (g.fst) fused_check_tail<K, RL>(g.fst, g.fslot, g.fblocks);
+}
+

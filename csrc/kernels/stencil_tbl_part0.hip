@@ -15,6 +15,11 @@ namespace hip {
   H3D_SEL##P(template void launch_tbl<T, R, WY, K, Q, N, S>(const StencilParams&, const KernelSpec&, hipStream_t);)
 #include "stencil_tbl_variants.inc"
 #undef H3D_V
+// ... and of the heat-source forms (stencil_tbl_src_variants.inc)
+#define H3D_VS(T, R, WY, K, Q, N, S, P) \
+  H3D_SEL##P(template void launch_tbl<T, R, WY, K, Q, N, S, true>(const StencilParams&, const KernelSpec&, hipStream_t);)
+#include "stencil_tbl_src_variants.inc"
+#undef H3D_VS
 
 }  // namespace hip
 }  // namespace heat3d

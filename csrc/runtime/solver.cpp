@@ -274,7 +274,7 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
       KernelSpec ks;
       ks.kind = kspec2_.kind;
       ks.K = K + 1;
-      ok = hip::lean_supported(dt_, ks);
+      ok = hip::lean_supported(dt_, ks, has_source_);
     }
     long_halo_ = ok;
     if (long_halo_)
@@ -431,6 +431,7 @@ Solver::~Solver() {
   for (auto& l : local_) {
     for (auto* f : l.field)
       if (f) be_->release(f);
+    if (l.source) be_->release(l.source);
     for (auto& io : l.faces) {
       be_->release(io.sendbuf);
       be_->release(io.recvbuf);
@@ -477,6 +478,25 @@ void Solver::preflight_memory() {
                  << " GB are free; use more ranks" << (dt_ == DType::F64 ? ", fp32" : "")
                  << (nbuf_ == 3 ? ", or two field buffers (--lag off)" : ""));
   }
+}
+
+// The heat source's extra field per local rank, counted when a source is set
+// (the fields are allocated by then: what must still fit is the source).
+void Solver::preflight_source() {
+  std::size_t extra = 0;
+  for (const auto& l : local_)
+    if (!l.source) extra += l.L.bytes();
+  std::size_t free_now = 0, total = 0;
+  const bool known = be_->mem_info(&free_now, &total);
+  if (known && cfg_.mem_preflight) {
+    const double reserve = cfg_.mem_reserve_gb * 1e9;
+    if ((double)extra + reserve > (double)free_now)
+      HEAT3D_THROW("memory preflight: the heat source needs " << extra / 1e9 << " GB more on this "
+                   << (be_->is_gpu() ? "GPU" : "host") << " (one more field per local subdomain) plus a "
+                   << reserve / 1e9 << " GB reserve, but only " << free_now / 1e9 << " of " << total / 1e9
+                   << " GB are free");
+  }
+  planned_bytes_ += extra;
 }
 
 bool Solver::is_root() const {
@@ -580,8 +600,18 @@ void Solver::initialize() {
   destroy_graphs();
   pending_.valid = false;
   init_fields();
+  retune();
+  initialized_ = true;
+  reset_state();
+  canary_stream_graphs();
+}
+
+// Start-up timing of the sweeps this run launches and the choices that follow
+// from it (initialize(); again when a heat source is set or cleared: the
+// source forms are kernels of their own, timed on their own)
+void Solver::retune() {
   sweep_costs_.clear();
-  if (pick_sweep_form()) {  // re-timed from the lean form on every initialisation
+  if (sweep_form_auto()) {  // re-timed from the lean form on every initialisation
     KernelSpec lean;
     lean.kind = kspec2_.kind;
     lean.K = K_;
@@ -600,11 +630,9 @@ void Solver::initialize() {
       const bool picked = (rl_pick_[Kp].O & kResidualLastOnly) != 0;
       ks_last_[Kp] = picked ? rl_pick_[Kp] : last_only(spec_for_depth(Kp));
       // (block decompositions: long sweeps keep every residual, see long_major_)
-      rl_d_[Kp] = hip::lean_supported(dt_, ks_last_[Kp]) && !(ordered_halo_ && Kp > K_);
+      rl_d_[Kp] = hip::lean_supported(dt_, ks_last_[Kp], has_source_) && !(ordered_halo_ && Kp > K_);
     }
   rl_ = rl_d_[K_];
-  reset_state();
-  canary_stream_graphs();
 }
 
 void Solver::init_fields() {
@@ -617,7 +645,7 @@ void Solver::init_fields() {
   }
 }
 
-void Solver::reset_state() {
+void Solver::reset_state(bool restart) {
   DeviceState hs;
   std::memset(&hs, 0, sizeof(hs));
   for (auto& r : hs.residual) r = kResidualInitBits;
@@ -640,7 +668,7 @@ void Solver::reset_state() {
   segs_.clear();
   seg_head_ = 0;
   sg_unchecked_ = false;
-  if (!cfg_.restart.empty()) load_checkpoint(cfg_.restart);
+  if (restart && !cfg_.restart.empty()) load_checkpoint(cfg_.restart);
   // make every pipeline event valid (complete) before the first iteration
   for (int i = 0; i < EV_COUNT; ++i) ev_valid_[i] = false;
   for (int p = 0; p < 2; ++p) {
@@ -816,7 +844,7 @@ void Solver::tune_schedules() {
     KernelSpec ks;
     ks.kind = kspec2_.kind;
     ks.K = K_ + 1;
-    if (hip::lean_supported(dt_, ks)) specs.push_back(ks);
+    if (hip::lean_supported(dt_, ks, has_source_)) specs.push_back(ks);
   }
   // the last-residual variants of those: kernels of their own, whose
   // schedules are timed (and looked up) separately
@@ -824,7 +852,7 @@ void Solver::tune_schedules() {
     const std::size_t nf = specs.size();
     for (std::size_t i = 0; i < nf; ++i) {
       const KernelSpec r = last_only(specs[i]);
-      if (hip::lean_supported(dt_, r)) specs.push_back(r);
+      if (hip::lean_supported(dt_, r, has_source_)) specs.push_back(r);
     }
   }
   for (const KernelSpec& ks : specs) {
@@ -836,6 +864,7 @@ void Solver::tune_schedules() {
       sp.in = l.field[0];
       sp.out = l.field[nxt(0)];
       sp.L = l.L;
+    sp.src = l.source;
       sp.box = box;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
@@ -885,6 +914,11 @@ KernelSpec Solver::spec_for_depth(int Kp) const {
 // hides its halo chain, the pair form timed 1 % faster and ran the same
 // (0.6775-0.6793 against 0.6776-0.6804 ms/step, gpurun_out/r7y).
 bool Solver::pick_sweep_form() const {
+  // (the pair kernel has no heat-source form: a source keeps the lean form)
+  return sweep_form_auto() && !has_source_;
+}
+
+bool Solver::sweep_form_auto() const {
   if (!tb_ || !be_->is_gpu() || dt_ != DType::F64 || has_halo_ || local_.size() != 1 || cfg_.kernel2 != "auto" ||
       kspec2_.kind != KernelSpec::TBL)
     return false;
@@ -915,7 +949,7 @@ void Solver::calibrate_remainders() {
     KernelSpec kl;
     kl.kind = kspec2_.kind;
     kl.K = K_ + 1;
-    if (!hip::lean_supported(dt_, kl)) return;
+    if (!hip::lean_supported(dt_, kl, has_source_)) return;
   }
   struct Events {  // released on every exit (a refused kernel variant throws)
     Backend* be;
@@ -933,6 +967,7 @@ void Solver::calibrate_remainders() {
       sp.in = l.field[0];
       sp.out = l.field[nxt(0)];
       sp.L = l.L;
+    sp.src = l.source;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
       sp.cu_reserved = be_->reserved_cus();
@@ -971,7 +1006,7 @@ void Solver::calibrate_remainders() {
   auto as_run = [&](const KernelSpec& f) {
     if (!rl_forms) return f;
     const KernelSpec r = last_only(f);
-    return hip::lean_supported(dt_, r) ? r : f;
+    return hip::lean_supported(dt_, r, has_source_) ? r : f;
   };
   std::vector<Cand> cands{{K_, as_run(kspec2_), "sweep" + std::to_string(K_), kspec2_},
                           {K_ + 1, as_run(spec_for_depth(K_ + 1)), "sweep" + std::to_string(K_ + 1),
@@ -983,7 +1018,7 @@ void Solver::calibrate_remainders() {
     // (the every-residual form spills: iteration 0's sweep and the replay of
     // one that converged run the default K + 1 shape)
     const KernelSpec t = KernelSpec::parse("tl4:1:4:1:12:0:3:66");
-    if (hip::lean_supported(dt_, t))
+    if (hip::lean_supported(dt_, t, has_source_))
       cands.push_back({K_ + 1, t, "sweep" + std::to_string(K_ + 1) + "[" + t.str() + "]", spec_for_depth(K_ + 1)});
   }
   const bool pick_form = pick_sweep_form();
@@ -992,14 +1027,14 @@ void Solver::calibrate_remainders() {
     cands.push_back({K_, pr, "sweep" + std::to_string(K_) + "[" + pr.resolved(dt_).str() + "]", pair_form()});
     KernelSpec pl = pair_form();  // and the pair form of the long sweep
     pl.K = K_ + 1;
-    if (hip::lean_supported(dt_, pl))
+    if (hip::lean_supported(dt_, pl, has_source_))
       cands.push_back({K_ + 1, as_run(pl), "sweep" + std::to_string(K_ + 1) + "[" + pl.resolved(dt_).str() + "]", pl});
   }
   for (int r = 1; r < K_; ++r) {
     if (r == 2 && dt_ == DType::F64 && kspec2_.kind == KernelSpec::TBL && be_->is_gpu()) {
       for (const char* v : {"tl2:1:5:1:16:0:3:2", "tl2:1:3:1:16:0:3:2", "tl2:2:6:1:8:0:3:2"}) {
         const KernelSpec ks = KernelSpec::parse(v);
-        if (hip::lean_supported(dt_, ks)) cands.push_back({2, as_run(ks), std::string("sweep2[") + v + "]", ks});
+        if (hip::lean_supported(dt_, ks, has_source_)) cands.push_back({2, as_run(ks), std::string("sweep2[") + v + "]", ks});
       }
       continue;
     }
@@ -1166,6 +1201,7 @@ int Solver::preheat(int sweeps) {
       sp.in = l.field[cur()];
       sp.out = l.field[nxt(cur())];
       sp.L = l.L;
+    sp.src = l.source;
       sp.box = l.tb_interior;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = dstate_;
@@ -1262,6 +1298,7 @@ void Solver::enqueue_iteration(int p, int bi) {
     sp.in = l.field[bi];
     sp.out = l.field[nxt(bi)];
     sp.L = l.L;
+    sp.src = l.source;
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1370,6 +1407,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
     sp.in = l.field[bi];
     sp.out = l.field[nxt(bi)];
     sp.L = l.L;
+    sp.src = l.source;
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1499,6 +1537,10 @@ bool Solver::fused_check() const {
 // converged in such a sweep (run() calls it on every rank).
 bool Solver::residual_last_ok() const {
   const double c = 1.0 - 2.0 * (phys_.D[0] + phys_.D[1] + phys_.D[2]);
+  // fp32 with a heat source: every residual (the source cancels in T'' - T'
+  // in exact arithmetic only; the fp32 rounding defect of the monotone check
+  //  is not extended to source runs)
+  if (has_source_ && dt_ == DType::F32) return false;
   return cfg_.monotone_check && be_->is_gpu() && tb_ && cfg_.verbose <= 0 && c >= 0.0 && fake_allreduce_us_ <= 0;
 }
 
@@ -1545,6 +1587,7 @@ void Solver::resolve_coarse() {
       sp.in = l.field[hit->inbuf];
       sp.out = l.field[nxt(hit->inbuf)];  // rewritten with the values it holds
       sp.L = l.L;
+    sp.src = l.source;
       sp.box = b;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = rstate_;
@@ -1751,6 +1794,7 @@ void Solver::finalize_converged(int64_t c) {
         sp.in = l.field[src];
         sp.out = l.field[dst];
         sp.L = l.L;
+    sp.src = l.source;
         sp.box = l.owned;
         const int64_t w = m - j;
         for (int a = 0; a < 3; ++a) {
@@ -1823,7 +1867,7 @@ int Solver::long_sweeps_for(int64_t n) const {
   KernelSpec ks;
   ks.kind = kspec2_.kind;
   ks.K = K_ + 1;
-  return be_->is_gpu() && !hip::lean_supported(dt_, ks) ? 0 : (int)b;
+  return be_->is_gpu() && !hip::lean_supported(dt_, ks, has_source_) ? 0 : (int)b;
 }
 
 bool Solver::graphs_allowed() const {
@@ -2361,3 +2405,4 @@ void Solver::inject(int idx, int64_t i, int64_t j, int64_t k, double value, bool
 }
 
 }  // namespace heat3d
+

@@ -21,6 +21,7 @@
 
 #include <array>
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -117,8 +118,31 @@ class Solver {
   // full sweeps check convergence from their last residual (residual_last_ok)
   bool monotone_check() const { return rl_; }
 
+  // Volumetric heat source, T_t = alpha lap(T) + q: `global_q` is the global
+  // array (N0*N1*N2 doubles, z fastest; every process passes the same one).
+  // Each local rank keeps S = dtype(dt * q) on its owned box plus its full
+  // ghost depth (zeros outside the grid); the source is static and never
+  // exchanged.  Setting or clearing it destroys the captured graphs, times the
+  // kernels that will run (the source forms are kernels of their own) and
+  // resets the convergence state to iteration 0; the field is kept.  Before
+  // initialize() it only stores the source (e.g. ahead of a --restart).
+  void set_source(const double* global_q);
+  void clear_source();
+  bool has_source() const { return has_source_; }
+  // User initial condition with its Dirichlet data: the boundary vertices of
+  // `global_T` become the fixed wall values, its interior T^0 (every rotation
+  // buffer, ghosts at full depth); iteration 0 follows.
+  void set_field(const double* global_T);
+  // the same from files (--source / --initial): raw little-endian float64,
+  // N0*N1*N2 values in the checkpoint field file's order; every rank reads
+  // only its own box; a wrong file size is a UsageError
+  void set_source_file(const std::string& path);
+  void set_field_file(const std::string& path);
+
   // Error vs analytic steady state (heat3D.cu:1093-1106, with a true global
-  // mean instead of rank-0's local value).  Uses the current field.
+  // mean instead of rank-0's local value).  Uses the current field.  Measured
+  // against T = y: only meaningful for the reference problem (no source, the
+  // default walls).
   void compute_error(double* global_mean, double* local_mean);
 
   // Field access.  gather_global fills `out` (N0*N1*N2 values as double,
@@ -225,6 +249,7 @@ class Solver {
     Subdomain sd;
     Layout L;
     void* field[3] = {nullptr, nullptr, nullptr};  // nbuf_ of them in use
+    void* source = nullptr;  // S = dtype(dt * q) in layout L, allocated by set_source
     Box owned, interior;
     std::vector<Box> shell;
     std::vector<FaceIO> faces;
@@ -244,7 +269,20 @@ class Solver {
   // field buffer, and the device state / schedule counters / events of
   // iteration 0 (restart: of the checkpoint)
   void init_fields();
-  void reset_state();
+  // restart: reload --restart's checkpoint (initialize(); not set_source / set_field)
+  void reset_state(bool restart = true);
+  void retune();
+  bool has_source_ = false;
+  bool initialized_ = false;
+  void preflight_source();
+  // copies n values of global row (gi, gj) from column gk on
+  using GlobalRows = std::function<void(int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst)>;
+  GlobalRows rows_of_array(const double* g) const;
+  GlobalRows rows_of_file(int fd) const;
+  void set_source_rows(const GlobalRows& rows);
+  void set_field_rows(const GlobalRows& rows);
+  void scatter_global(const GlobalRows& rows, double scale, const Local& l, void* const* bufs, int nbufs);
+  void consolidate_fields();
   // Start-up canary of the per-stream graphs (initialize(), every rank at the
   // same point): one schedule cycle eagerly, then the same cycle as per-stream
   // graphs with the device-side waits' timeout cut to --graph-canary; a
@@ -358,6 +396,7 @@ class Solver {
   std::vector<std::pair<std::string, double>> sweep_costs_;  // start-up timings (ms per sweep)
   void calibrate_remainders();
   bool pick_sweep_form() const;
+  bool sweep_form_auto() const;
   KernelSpec pair_form() const;
   int last_bnd_ = 0;          // boundary-layer depth of the last overlapped sweep (0: none pending)
   bool ordered_halo_ = false; // axis-ordered exchange filling edges / corners (deep y / z halos)

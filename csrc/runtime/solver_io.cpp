@@ -407,6 +407,8 @@ void Solver::save_checkpoint(const std::string& dir) {
     j.set_raw("dims", "[" + std::to_string(dec_.topo.dims[0]) + ", " + std::to_string(dec_.topo.dims[1]) +
                           ", " + std::to_string(dec_.topo.dims[2]) + "]");
     j.set("layout", std::string("global z-fastest, N0*N1*N2 values"));
+    // the source itself is not written: the caller sets it again before a restart
+    j.set_raw("has_source", has_source_ ? "true" : "false");
     io::write_file_atomic(dir + "/meta.json", j.dump() + "\n");
     // older field files, and the temp files of saves that a crash
     // interrupted (a full-grid field.<iter>.raw.tmp each)
@@ -430,6 +432,10 @@ void Solver::load_checkpoint(const std::string& dir) {
                            std::to_string(dec_.N[2]) + "]";
   HEAT3D_CHECK(meta["N"] == Nexp, "checkpoint grid " << meta["N"] << " != run grid " << Nexp);
   HEAT3D_CHECK(meta["dtype"] == dtype_name(dt_), "checkpoint dtype " << meta["dtype"] << " != " << dtype_name(dt_));
+  // (checkpoints older than the heat source have no such key)
+  HEAT3D_CHECK(!(meta.count("has_source") && meta["has_source"] == "true") || has_source_,
+               "checkpoint " << dir << " was written with a heat source, which is not stored in it: set the source "
+                                       "again (set_source / --source) before loading it");
   const int64_t it = std::atoll(meta["iteration"].c_str());
   const double norm = std::atof(meta["norm"].c_str());
   const int64_t* N = dec_.N;
@@ -508,6 +514,149 @@ void Solver::load_checkpoint(const std::string& dir) {
   be_->sync(kCompute);
   issued_ = it;
   cur_ = 0;
+}
+
+// Scatter a global array (N0*N1*N2 doubles, z fastest; `rows` copies a run of
+// one of its z rows, from memory or from a file) into a local field in
+// the padded layout: the owned box and the full ghost depth of every axis
+// (deep halos included) straight from the array, rounded to the field dtype
+// after scaling by `scale` in double; points outside the global grid, and the
+// layout's padding, are 0.  Whole x planes are staged through the host.
+void Solver::scatter_global(const GlobalRows& rows, double scale, const Local& l, void* const* bufs, int nbufs) {
+  const Layout& L = l.L;
+  const int64_t* N = dec_.N;
+  for (int b = 0; b < nbufs; ++b) be_->memset(bufs[b], 0, L.bytes(), kCompute);
+  const int64_t planes = L.n[0] + 2 * L.gx;
+  const int64_t pb = L.sx * (int64_t)esize_;
+  const int64_t xc = std::max<int64_t>(1, std::min<int64_t>(planes, (int64_t)io_stage_bytes(cfg_) / pb));
+  std::vector<char> host((std::size_t)(xc * pb));
+  std::vector<double> rowbuf;
+  for (int64_t x0 = 0; x0 < planes; x0 += xc) {
+    const int64_t nx = std::min(xc, planes - x0);
+    std::memset(host.data(), 0, (std::size_t)(nx * pb));
+    for (int64_t ii = 0; ii < nx; ++ii) {
+      const int64_t i = x0 + ii - L.gx, gi = l.sd.gstart[0] + i;
+      if (gi < 0 || gi >= N[0]) continue;
+      for (int64_t j = -L.gy; j < L.n[1] + L.gy; ++j) {
+        const int64_t gj = l.sd.gstart[1] + j;
+        if (gj < 0 || gj >= N[1]) continue;
+        const int64_t k0 = std::max<int64_t>(-L.gz, -l.sd.gstart[2]);
+        const int64_t k1 = std::min<int64_t>(L.n[2] + L.gz, N[2] - l.sd.gstart[2]);
+        if (k1 <= k0) continue;
+        rowbuf.resize((std::size_t)(k1 - k0));
+        rows(gi, gj, l.sd.gstart[2] + k0, k1 - k0, rowbuf.data());
+        const double* row = rowbuf.data() - k0;
+        // element index inside the staged chunk (plane ii of it)
+        const int64_t e0 = ii * L.sx + (j + L.gy) * L.sy + L.zoff;
+        if (dt_ == DType::F64) {
+          double* d = reinterpret_cast<double*>(host.data()) + e0;
+          for (int64_t k = k0; k < k1; ++k) d[k] = scale * row[k];
+        } else {
+          float* d = reinterpret_cast<float*>(host.data()) + e0;
+          for (int64_t k = k0; k < k1; ++k) d[k] = static_cast<float>(scale * row[k]);
+        }
+      }
+    }
+    for (int b = 0; b < nbufs; ++b)
+      be_->copy(static_cast<char*>(bufs[b]) + x0 * pb, host.data(), (std::size_t)(nx * pb), CopyKind::H2D, kCompute);
+    be_->sync(kCompute);
+  }
+}
+
+// Every buffer of the rotation gets the current field (as after init_fields or
+// a restart), so that the schedule can restart from buffer 0.
+void Solver::consolidate_fields() {
+  if (cur_ == 0 && issued_ == 0) return;
+  for (auto& l : local_)
+    for (int b = 0; b < nbuf_; ++b)
+      if (b != cur_) be_->copy(l.field[b], l.field[cur_], l.L.bytes(), CopyKind::D2D, kCompute);
+  be_->sync(kCompute);
+}
+
+Solver::GlobalRows Solver::rows_of_array(const double* g) const {
+  const int64_t* N = dec_.N;
+  return [g, N](int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst) {
+    std::memcpy(dst, g + (gi * N[1] + gj) * N[2] + gk, (std::size_t)n * sizeof(double));
+  };
+}
+
+// raw little-endian float64, N0*N1*N2 values, z fastest (the checkpoint field
+// file's order): every rank reads only the rows of its own ghosted box
+Solver::GlobalRows Solver::rows_of_file(int fd) const {
+  const int64_t* N = dec_.N;
+  return [fd, N](int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst) {
+    io::pread_all(fd, reinterpret_cast<char*>(dst), n * (int64_t)sizeof(double),
+                  ((gi * N[1] + gj) * N[2] + gk) * (int64_t)sizeof(double));
+  };
+}
+
+static int open_global_file(const std::string& path, const int64_t N[3], const char* what) {
+  const int64_t want = N[0] * N[1] * N[2] * (int64_t)sizeof(double);
+  if (io::file_size(path) != want)
+    throw UsageError(std::string(what) + " file " + path + " has " + std::to_string(io::file_size(path)) +
+                     " bytes, expected " + std::to_string(want) + " (NX*NY*NZ float64 values)");
+  return io::open_raw(path, false);
+}
+
+void Solver::set_source_file(const std::string& path) {
+  const int fd = open_global_file(path, dec_.N, "--source");
+  set_source_rows(rows_of_file(fd));
+  io::close_raw(fd);
+}
+
+void Solver::set_field_file(const std::string& path) {
+  const int fd = open_global_file(path, dec_.N, "--initial");
+  set_field_rows(rows_of_file(fd));
+  io::close_raw(fd);
+}
+
+void Solver::set_source(const double* global_q) { set_source_rows(rows_of_array(global_q)); }
+void Solver::set_field(const double* global_T) { set_field_rows(rows_of_array(global_T)); }
+
+void Solver::set_source_rows(const GlobalRows& rows) {
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  preflight_source();
+  for (auto& l : local_) {
+    if (!l.source) l.source = be_->alloc(l.L.bytes());
+    void* bufs[1] = {l.source};
+    // S = dtype(dt * q): the product in double, rounded once
+    scatter_global(rows, phys_.dt, l, bufs, 1);
+  }
+  has_source_ = true;
+  if (!initialized_) return;  // initialize() times the source forms
+  consolidate_fields();
+  retune();
+  reset_state(false);
+}
+
+void Solver::clear_source() {
+  if (!has_source_) return;
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  for (auto& l : local_) {
+    planned_bytes_ -= std::min(planned_bytes_, l.L.bytes());
+    be_->release(l.source);
+    l.source = nullptr;
+  }
+  has_source_ = false;
+  if (!initialized_) return;
+  consolidate_fields();
+  retune();
+  reset_state(false);
+}
+
+void Solver::set_field_rows(const GlobalRows& rows) {
+  HEAT3D_CHECK(initialized_, "set_field: initialize() first (it would overwrite the field)");
+  be_->sync_all();
+  pending_.valid = false;
+  for (auto& l : local_) {
+    void* bufs[3] = {l.field[0], l.field[1], l.field[2]};
+    scatter_global(rows, 1.0, l, bufs, nbuf_);
+  }
+  reset_state(false);
 }
 
 }  // namespace heat3d

@@ -67,6 +67,17 @@ class HeatEquation3D:
         y = np.arange(self.n[1], dtype=np.float64) * self.h[1]
         return np.broadcast_to(y[None, :, None], self.n).copy()
 
+    def sine_source(self, amplitude: float) -> np.ndarray:
+        """Heat source q = alpha * lam_h * A * sin(pi x) sin(pi y) sin(pi z) on the grid,
+        with lam_h = sum_d (4 / h_d^2) sin^2(pi h_d / 2) the eigenvalue of the
+        discrete Laplacian for that mode: the discrete steady state of
+        T_t = alpha lap(T) + q with the reference's walls is exactly
+        y + A sin(pi x) sin(pi y) sin(pi z)."""
+        h = self.h
+        lam = sum(4.0 / hd ** 2 * np.sin(np.pi * hd / 2.0) ** 2 for hd in h)
+        sx, sy, sz = (np.sin(np.pi * np.arange(n, dtype=np.float64) * hd) for n, hd in zip(self.n, h))
+        return (self.alpha * lam * float(amplitude)) * sx[:, None, None] * sy[None, :, None] * sz[None, None, :]
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -189,6 +200,37 @@ class HeatSolver:
 
     def synchronize(self) -> None:
         self._s.synchronize()
+
+    # -- problem definition ----------------------------------------------------
+    def _global_array(self, a, what: str) -> np.ndarray:
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+        if a.shape != tuple(self.model.n):
+            raise ValueError(f"{what}: shape {a.shape} != grid {tuple(self.model.n)}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"{what}: non-finite values")
+        return a
+
+    def set_source(self, q) -> None:
+        """Volumetric heat source: T_t = alpha lap(T) + q, ``q`` an array of the
+        global shape (every rank of a multi-process job passes the same array;
+        each keeps its own box).  The update adds S = dtype(dt * q) to every
+        updated point.  Keeps the field, restarts the iteration count and the
+        convergence state at 0.  Collective."""
+        q = self._global_array(q, "set_source")
+        self._ensure()
+        self._s.set_source(q)
+
+    def clear_source(self) -> None:
+        self._s.clear_source()
+
+    def set_field(self, T) -> None:
+        """User initial condition with its Dirichlet data: the boundary vertices
+        of ``T`` (global shape) become the fixed wall values, its interior T^0;
+        iteration 0 follows.  ``error_percent`` keeps measuring against T = y,
+        which is only meaningful for the reference problem.  Collective."""
+        T = self._global_array(T, "set_field")
+        self._ensure()
+        self._s.set_field(T)
 
     def prepare_steps(self, n: int) -> None:
         """Capture (untimed) the hipGraph that ``step(n)`` will replay."""

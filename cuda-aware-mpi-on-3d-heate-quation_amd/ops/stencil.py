@@ -74,10 +74,24 @@ def _stream_ptr(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _source_ptr(src: PaddedField, source: Optional[PaddedField]) -> int:
+    """Pointer of the heat-source field S = dtype(dt * q) (0: none); it must
+    share the field's layout (ghost shells included), dtype and device."""
+    if source is None:
+        return 0
+    if source.layout != src.layout or source.dtype != src.dtype or source.device != src.device:
+        raise ValueError("the source field must share the field's layout, dtype and device")
+    return source.data_ptr()
+
+
 def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
               box: Optional[Sequence[int]] = None, kernel: str = "auto",
-              state: Optional[torch.Tensor] = None, slot: int = 0) -> None:
+              state: Optional[torch.Tensor] = None, slot: int = 0,
+              source: Optional[PaddedField] = None) -> None:
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
+
+    ``source``: optional field S = dtype(dt * q) in the same layout, added to
+    every updated point (kernels.hpp ftcs_update_src).
 
     ``state``: optional uint8/int64 tensor of ``DEVICE_STATE_BYTES`` that
     receives the fused max-residual (IEEE bits of a double in its first
@@ -96,11 +110,12 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
             raise ValueError("state tensor too small or on the wrong device")
         sptr = state.data_ptr()
     ext = native()
+    qptr = _source_ptr(src, source)
     if src.device.type == "cuda":
         ext.hip.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot,
-                        kernel, _stream_ptr(src.flat))
+                        kernel, _stream_ptr(src.flat), qptr)
     else:
-        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot)
+        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr)
 
 
 def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: str = "auto",
@@ -128,12 +143,13 @@ def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: s
 
 def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int],
           ux: Sequence[int] = (0, -1), kernel: str = "tl3", state: Optional[torch.Tensor] = None,
-          slot: int = 0) -> None:
+          slot: int = 0, source: Optional[PaddedField] = None) -> None:
     """One K-step sweep (K from ``kernel``: tl2..tl6) on ``box``
     = (x0, x1, y0, y1, z0, z1) of a deep-ghost field, with the intermediate
     steps computed on the x range ``ux`` (the solver's x-slab schedule).
     GPU tensors run the gfx950 kernel, CPU tensors the K-single-steps
-    definition (csrc/kernels/kernels_cpu.cpp)."""
+    definition (csrc/kernels/kernels_cpu.cpp).  ``source``: optional heat-source
+    field S in the same layout, added at every step."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -143,18 +159,21 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
         sptr = state.data_ptr()
     args = (src.dt, src.data_ptr(), dst.data_ptr(), list(src.n), src.gx, list(box), list(ux), list(D), sptr, slot,
             kernel)
+    qptr = _source_ptr(src, source)
     if src.device.type == "cuda":
-        native().hip.stencil_sweep(*args, _stream_ptr(src.flat))
+        native().hip.stencil_sweep(*args, _stream_ptr(src.flat), qptr)
     else:
-        native().cpu.stencil_sweep(*args)
+        native().cpu.stencil_sweep(*args, qptr)
 
 
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
-           kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0) -> None:
+           kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0,
+           source: Optional[PaddedField] = None) -> None:
     """K-step sweep with deep ghosts on every axis (the block-decomposition
     schedule): ``u`` = (ux0, ux1, uy0, uy1, uz0, uz1) are the update ranges of
     the intermediate steps.  GPU tensors run the lean kernel, CPU tensors the
-    K-single-steps definition."""
+    K-single-steps definition.  ``source``: optional heat-source field S in the
+    same layout (deep ghosts included), added at every step."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -164,10 +183,11 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
         sptr = state.data_ptr()
     args = (src.dt, src.data_ptr(), dst.data_ptr(), list(src.n), [src.gx, src.gy, src.gz], list(box), list(u),
             list(D), sptr, slot, kernel)
+    qptr = _source_ptr(src, source)
     if src.device.type == "cuda":
-        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat))
+        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr)
     else:
-        native().cpu.stencil_sweep3(*args)
+        native().cpu.stencil_sweep3(*args, qptr)
 
 
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
@@ -188,8 +208,13 @@ def unpack_box(f: PaddedField, box: Sequence[int], buf: torch.Tensor) -> None:
     native().hip.unpack_box(f.dt, f.data_ptr(), list(f.n), list(box), buf.data_ptr(), _stream_ptr(f.flat))
 
 
-def ftcs_reference(T: torch.Tensor, D: Sequence[float]) -> Tuple[torch.Tensor, float]:
+def ftcs_reference(T: torch.Tensor, D: Sequence[float],
+                   src: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, float]:
     """Plain-PyTorch FTCS on a ghosted block; returns (new interior, max |dT|).
+
+    ``src``: optional heat source S = dtype(dt * q) on the interior points
+    (shape of the result), added with one rounded addition after the update
+    (kernels.hpp ftcs_update_src).
 
     Same arithmetic as the native backends (exactly rounded FMAs emulated with
     error-free transformations, utils/fma.py), so results compare bitwise."""
@@ -198,6 +223,8 @@ def ftcs_reference(T: torch.Tensor, D: Sequence[float]) -> Tuple[torch.Tensor, f
     c = T[1:-1, 1:-1, 1:-1]
     new = ftcs_update(c, T[:-2, 1:-1, 1:-1], T[2:, 1:-1, 1:-1], T[1:-1, :-2, 1:-1], T[1:-1, 2:, 1:-1],
                       T[1:-1, 1:-1, :-2], T[1:-1, 1:-1, 2:], D)
+    if src is not None:
+        new = new + src.to(new.dtype)
     # residual in the field's precision (kernels.hpp resid_abs), widened for the max
     res = (new - c).abs().max().double().item() if new.numel() else 0.0
     return new, res
