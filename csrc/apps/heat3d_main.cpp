@@ -83,6 +83,20 @@ static int drive(const Config& cfg, Solver& solver) {
   // source needs it, and the start-up timing then runs the source kernels),
   // the initial field after it
   if (!cfg.source_file.empty()) solver.set_source_file(cfg.source_file);
+  // (the conductivity too: no sweep is timed for a run of single steps)
+  if (!cfg.conductivity_file.empty()) {
+    try {
+      solver.set_conductivity_file(cfg.conductivity_file);
+    } catch (const UsageError& e) {
+      // values outside (0, 1]: a usage error that only the solver can find
+      // (every rank throws alike; the root prints, as for a bad command line)
+      if (root) {
+        std::cout << Config::usage() << std::flush;
+        std::cerr << "heat3d: " << e.what() << std::endl;
+      }
+      return 1;
+    }
+  }
   solver.initialize();
   if (!cfg.initial_file.empty()) solver.set_field_file(cfg.initial_file);
   RunResult r = solver.run();

@@ -105,6 +105,8 @@ std::string Config::usage() {
      << "  --restart DIR             resume from a checkpoint directory\n"
      << "  --source FILE             volumetric heat source q (T_t = alpha lap(T) + q): raw little-endian\n"
      << "                            float64, NX*NY*NZ values, z fastest (the checkpoint field file's order)\n"
+     << "  --conductivity FILE       relative conductivity c, 0 < c <= 1 (T_t = div(alpha c grad T) + q), same format\n"
+     << "                            as --source; iterations then run as single steps (no K-step sweeps)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -250,6 +252,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--restart") c.restart = get("--restart");
     else if (key == "--source") c.source_file = get("--source");
     else if (key == "--initial") c.initial_file = get("--initial");
+    else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--json-out") c.json_out = get("--json-out");
     else if (key == "--verbose") c.verbose = (int)to_i64(get("--verbose"), "--verbose");
     else if (key == "--progress") c.progress_s = to_f64(get("--progress"), "--progress");
@@ -352,10 +355,10 @@ Config Config::parse(int argc, const char* const* argv) {
   if (c.watchdog_s <= 0) throw UsageError("--watchdog must be > 0");
   if (c.progress_s < 0) throw UsageError("--progress must be >= 0");
   if (c.time_limit_s < 0) throw UsageError("--time-limit must be >= 0");
-  // --source / --initial: NX*NY*NZ float64 values; a wrong size is a usage error
-  for (const auto* f : {&c.source_file, &c.initial_file}) {
+  // --source / --initial / --conductivity: NX*NY*NZ float64 values; a wrong size is a usage error
+  for (const auto* f : {&c.source_file, &c.initial_file, &c.conductivity_file}) {
     if (f->empty()) continue;
-    const char* flag = f == &c.source_file ? "--source" : "--initial";
+    const char* flag = f == &c.source_file ? "--source" : f == &c.initial_file ? "--initial" : "--conductivity";
     struct stat st {};
     if (::stat(f->c_str(), &st) != 0) throw UsageError(std::string(flag) + ": cannot read file " + *f);
     const long long want = (long long)c.n[0] * c.n[1] * c.n[2] * 8;
@@ -364,8 +367,10 @@ Config Config::parse(int argc, const char* const* argv) {
                        " bytes, expected " + std::to_string(want) + " (NX*NY*NZ little-endian float64 values)");
   }
   if (!c.initial_file.empty() && !c.restart.empty()) throw UsageError("--initial and --restart are exclusive");
-  if ((!c.source_file.empty() || !c.initial_file.empty()) && c.scheme == "reference")
-    throw UsageError("--source / --initial are not part of --scheme reference");
+  if ((!c.source_file.empty() || !c.initial_file.empty() || !c.conductivity_file.empty()) && c.scheme == "reference")
+    throw UsageError("--source / --initial / --conductivity are not part of --scheme reference");
+  if (!c.conductivity_file.empty() && c.compat)
+    throw UsageError("--conductivity is not part of --compat (the reference's uniform material)");
   return c;
 }
 

@@ -66,6 +66,7 @@ struct Config {
   std::string checkpoint_dir;
   std::string restart;
   std::string source_file;   // --source: heat source q, raw float64 NX*NY*NZ
+  std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   std::string json_out;
   int verbose = 0;

@@ -36,6 +36,25 @@ static inline double row(const Real* __restrict in, Real* __restrict out, const 
   return nan ? std::nan("") : lres;
 }
 
+template <typename Real, bool SRC>
+static inline double row_var(const Real* __restrict in, Real* __restrict out, const Real* __restrict h,
+                             const Real* __restrict src, int64_t n, int64_t sx, int64_t sy, Real Dx, Real Dy,
+                             Real Dz) {
+  double lres = 0.0;
+  bool nan = false;
+  for (int64_t k = 0; k < n; ++k) {
+    const Real T = in[k];
+    Real nv = ftcs_update_var<Real>(T, in[k - sx], in[k + sx], in[k - sy], in[k + sy], in[k - 1], in[k + 1], h[k],
+                                    h[k - sx], h[k + sx], h[k - sy], h[k + sy], h[k - 1], h[k + 1], Dx, Dy, Dz);
+    if constexpr (SRC) nv = add_source<Real>(nv, src[k]);
+    out[k] = nv;
+    const double d = resid_abs(nv, T);
+    nan |= d != d;
+    lres = d > lres ? d : lres;
+  }
+  return nan ? std::nan("") : lres;
+}
+
 double ftcs_row_f64(const double* in, double* out, int64_t n, int64_t sx, int64_t sy, double Dx, double Dy,
                     double Dz) {
   return row<double, false>(in, out, nullptr, n, sx, sy, Dx, Dy, Dz);
@@ -52,6 +71,17 @@ double ftcs_row_src_f32(const float* in, float* out, const float* src, int64_t n
   return row<float, true>(in, out, src, n, sx, sy, Dx, Dy, Dz);
 }
 
+double ftcs_row_var_f64(const double* in, double* out, const double* cond, const double* src, int64_t n, int64_t sx,
+                        int64_t sy, double Dx, double Dy, double Dz) {
+  return src ? row_var<double, true>(in, out, cond, src, n, sx, sy, Dx, Dy, Dz)
+             : row_var<double, false>(in, out, cond, nullptr, n, sx, sy, Dx, Dy, Dz);
+}
+double ftcs_row_var_f32(const float* in, float* out, const float* cond, const float* src, int64_t n, int64_t sx,
+                        int64_t sy, float Dx, float Dy, float Dz) {
+  return src ? row_var<float, true>(in, out, cond, src, n, sx, sy, Dx, Dy, Dz)
+             : row_var<float, false>(in, out, cond, nullptr, n, sx, sy, Dx, Dy, Dz);
+}
+
 }  // namespace H3D_ROWS_NS
 
 #ifdef H3D_ROWS_DISPATCH
@@ -60,9 +90,10 @@ const RowKernels& cpu_row_kernels() {
     __builtin_cpu_init();
     if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"))
       return RowKernels{rows_fma::ftcs_row_f64, rows_fma::ftcs_row_f32, "x86-64+fma+avx2", rows_fma::ftcs_row_src_f64,
-                        rows_fma::ftcs_row_src_f32};
+                        rows_fma::ftcs_row_src_f32, rows_fma::ftcs_row_var_f64, rows_fma::ftcs_row_var_f32};
     return RowKernels{rows_generic::ftcs_row_f64, rows_generic::ftcs_row_f32, "x86-64 (libm fma)",
-                      rows_generic::ftcs_row_src_f64, rows_generic::ftcs_row_src_f32};
+                      rows_generic::ftcs_row_src_f64, rows_generic::ftcs_row_src_f32, rows_generic::ftcs_row_var_f64,
+                      rows_generic::ftcs_row_var_f32};
   }();
   return k;
 }

@@ -25,12 +25,20 @@ template <typename Real>
 using FtcsRowSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t sx, int64_t sy,
                                 Real Dx, Real Dy, Real Dz);
 
+// with a conductivity field: out[k] = ftcs_update_var(in[k], ..., cond[k], ...),
+// plus src[k] where src != nullptr (ftcs_update_var_src)
+template <typename Real>
+using FtcsRowVarFn = double (*)(const Real* in, Real* out, const Real* cond, const Real* src, int64_t n, int64_t sx,
+                                int64_t sy, Real Dx, Real Dy, Real Dz);
+
 struct RowKernels {
   FtcsRowFn<double> f64;
   FtcsRowFn<float> f32;
   const char* isa;
   FtcsRowSrcFn<double> src_f64;
   FtcsRowSrcFn<float> src_f32;
+  FtcsRowVarFn<double> var_f64;
+  FtcsRowVarFn<float> var_f32;
 };
 
 const RowKernels& cpu_row_kernels();
@@ -40,12 +48,20 @@ double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, d
 double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
 double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
 double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
+double ftcs_row_var_f64(const double*, double*, const double*, const double*, int64_t, int64_t, int64_t, double,
+                        double, double);
+double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
+                        float);
 }  // namespace rows_generic
 namespace rows_fma {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
 double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
 double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
 double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
+double ftcs_row_var_f64(const double*, double*, const double*, const double*, int64_t, int64_t, int64_t, double,
+                        double, double);
+double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
+                        float);
 }  // namespace rows_fma
 
 }  // namespace cpu

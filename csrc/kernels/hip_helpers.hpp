@@ -193,6 +193,8 @@ __device__ __forceinline__ bool flag_set(const int* done) {
   return done != nullptr && __builtin_nontemporal_load(done) != 0;
 }
 
+// K-step sweeps have no conductivity form: throws when p.cond is set (stencil_tbl.hip)
+void refuse_conductivity(const StencilParams& p, const KernelSpec& k);
 // Resident workgroups of `kernel` on the whole device (occupancy x CUs).
 int device_slots(const void* kernel, int block);
 // x-segment length for an x-marching kernel with `halo` extra planes per segment.

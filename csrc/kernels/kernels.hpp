@@ -77,6 +77,12 @@ struct StencilParams {
   // in/out (ghost shells included), added to every updated point
   // (ftcs_update_src).  nullptr: no source, the kernels without a source term.
   const void* src = nullptr;
+  // relative conductivity, stored as Ch = dtype(0.5 * c) with 0 < c <= 1: a
+  // static field in the same Layout (ghost shells included; a face weight
+  // towards a ghost point reads Ch there).  Every updated point is evaluated
+  // by ftcs_update_var.  nullptr: uniform material, the kernels above.  Only
+  // single-step kernels have a conductivity form (a sweep with it is an error).
+  const void* cond = nullptr;
 };
 
 struct InitParams {
@@ -101,6 +107,8 @@ H3D_HD inline double boundary_value(int64_t gi, int64_t gj, int64_t gk, const in
 namespace hip {
 void init_field(DType t, const InitParams& p, void* stream);
 void stencil(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
+// its conductivity forms (stencil_var.hip; stencil() dispatches here when p.cond is set)
+void stencil_var(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 // K-step temporally blocked sweep, lean kernel (stencil_tbl.hip), K = k.K
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 // z tile stride of the lean kernel for a box (host-side choice, stencil_tbl.hip)
@@ -246,6 +254,47 @@ template <typename Real>
 H3D_HD inline Real ftcs_update_src(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real Dx,
                                    Real Dy, Real Dz, Real S) {
   return add_source<Real>(ftcs_update<Real>(c, xm, xp, ym, yp, zm, zp, Dx, Dy, Dz), S);
+}
+
+// FTCS update with a spatially varying conductivity, T_t = div(kappa grad T),
+// kappa = alpha * c(x, y, z), 0 < c <= 1.  The stored field is Ch = dtype(0.5 c)
+// (scaled in double, rounded once), so the weight of a face, the arithmetic
+// mean of c at its two vertices, is one plain rounded add, Ch[p] + Ch[q].  The
+// add commutes: both cells of a face compute the same bit pattern, and the
+// flux fx = w (T[q] - T[p]) that leaves one is exactly the flux that enters
+// the other (the form is conservative).  Per axis
+//   f = fma(w+, T+ - T, w- * (T- - T)),
+// then T' = fma(Dz, fz, fma(Dy, fy, fma(Dx, fx, T))).  Arguments: the field's
+// seven points, then Ch at the same seven points.  With c == 1 everywhere it
+// equals ftcs_update up to rounding, not bitwise.  With c <= 1 the centre
+// weight 1 - sum_a D_a (w_a+ + w_a-) stays >= 1 - 2 (Dx + Dy + Dz) >= 0: the
+// update is a convex combination under the time step of the uniform problem.
+template <typename Real>
+H3D_HD inline Real var_flux(Real c, Real m, Real p, Real wm, Real wp) {
+  return h3d_fma(wp, p - c, wm * (m - c));
+}
+// the update from the six face weights (kernels that carry a weight from one
+// point to the next: w- of a point is w+ of its predecessor, bit for bit)
+template <typename Real>
+H3D_HD inline Real ftcs_update_varw(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real wxm, Real wxp,
+                                    Real wym, Real wyp, Real wzm, Real wzp, Real Dx, Real Dy, Real Dz) {
+  const Real fx = var_flux<Real>(c, xm, xp, wxm, wxp);
+  const Real fy = var_flux<Real>(c, ym, yp, wym, wyp);
+  const Real fz = var_flux<Real>(c, zm, zp, wzm, wzp);
+  return h3d_fma(Dz, fz, h3d_fma(Dy, fy, h3d_fma(Dx, fx, c)));
+}
+template <typename Real>
+H3D_HD inline Real ftcs_update_var(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real hc, Real hxm,
+                                   Real hxp, Real hym, Real hyp, Real hzm, Real hzp, Real Dx, Real Dy, Real Dz) {
+  return ftcs_update_varw<Real>(c, xm, xp, ym, yp, zm, zp, hc + hxm, hc + hxp, hc + hym, hc + hyp, hc + hzm,
+                                hc + hzp, Dx, Dy, Dz);
+}
+template <typename Real>
+H3D_HD inline Real ftcs_update_var_src(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real hc,
+                                       Real hxm, Real hxp, Real hym, Real hyp, Real hzm, Real hzp, Real Dx, Real Dy,
+                                       Real Dz, Real S) {
+  return add_source<Real>(
+      ftcs_update_var<Real>(c, xm, xp, ym, yp, zm, zp, hc, hxm, hxp, hym, hyp, hzm, hzp, Dx, Dy, Dz), S);
 }
 
 // Residual term of one point, |T^{n+1} - T^n|, taken in the field's

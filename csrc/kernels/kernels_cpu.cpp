@@ -78,7 +78,12 @@ static void stencil_t(const StencilParams& p) {
     if constexpr (sizeof(Real) == 8) return cpu_row_kernels().src_f64;
     else return cpu_row_kernels().src_f32;
   }();
+  const auto rowvar = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().var_f64;
+    else return cpu_row_kernels().var_f32;
+  }();
   const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
+  const Real* __restrict cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
   const int64_t nk = b.extent(2);
 #pragma omp parallel for collapse(2) schedule(static) reduction(max : resbits) if (omp_worth(b.volume()))
   for (int64_t i = b.lo[0]; i < b.hi[0]; ++i)
@@ -86,6 +91,7 @@ static void stencil_t(const StencilParams& p) {
       const int64_t c = L.index(i, j, b.lo[2]);
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
       const double lres = nk <= 0 ? 0.0
+                          : cond  ? rowvar(in + c, out + c, cond + c, src ? src + c : nullptr, nk, sx, sy, Dx, Dy, Dz)
                           : src   ? rowsrc(in + c, out + c, src + c, nk, sx, sy, Dx, Dy, Dz)
                                   : rowfn(in + c, out + c, nk, sx, sy, Dx, Dy, Dz);
       unsigned long long bits;

@@ -593,6 +593,7 @@ static void dispatch_tile(const StencilParams& p, const KernelSpec& ks, hipStrea
 
 void stencil(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   if (p.box.empty()) return;
+  if (p.cond) return stencil_var(t, p, k, stream);  // conductivity forms (stencil_var.hip)
   if (k.kind == KernelSpec::Naive) {
     if (t == DType::F64) launch_naive<double>(p, S(stream));
     else launch_naive<float>(p, S(stream));

@@ -204,6 +204,7 @@ bool lean_supported(DType t, const KernelSpec& k, bool with_source) {
 }
 
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
+  refuse_conductivity(p, k);
   if (p.box.empty()) return;
   if (p.src) {
     const bool ok =
@@ -227,6 +228,13 @@ void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* st
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   HEAT3D_CHECK(k.multi_step(), "sweep needs a K-step kernel (tl2..tl6)");
   stencil_lean(t, p, k, stream);
+}
+
+// (every K-step launch comes through stencil_lean or stencil_lean_pair)
+void refuse_conductivity(const StencilParams& p, const KernelSpec& k) {
+  if (p.cond)
+    HEAT3D_THROW("K-step sweep kernel " << k.str() << " has no conductivity form: with a conductivity field every "
+                                                     "iteration runs as a single step (tile | naive)");
 }
 
 }  // namespace hip

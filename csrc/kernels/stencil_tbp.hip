@@ -563,6 +563,7 @@ bool lean_pair_supported(DType t, const KernelSpec& k) {
 }
 
 void stencil_lean_pair(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
+  refuse_conductivity(p, k);
   if (p.box.empty()) return;
   const bool ok = t == DType::F64 ? run_tbp<double>(&p, k, S(stream)) : run_tbp<float>(&p, k, S(stream));
   if (!ok) {

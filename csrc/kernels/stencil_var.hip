@@ -1,0 +1,341 @@
+// heat3d-mi355x — single-step gfx950 kernels with a spatially varying
+// conductivity (kernels.hpp ftcs_update_var): T_t = div(kappa grad T) [+ q].
+//
+// A translation unit of its own, so that the uniform-material kernels of
+// kernels_hip.hip keep their code.  hip::stencil dispatches here when
+// StencilParams::cond is set.
+//   * stencil_var_tile: the structure of the uniform tile kernel
+//     (stencil_tile_kernel.inc): a workgroup of WZ x WY waves marches a
+//     (rows x z) tile along x, the field's x-1 / x / x+1 planes in a register
+//     queue, y neighbour rows through LDS, z neighbours through DPP, one
+//     barrier per plane, fused residual, the done flag, XCD-aware block order.
+//     The conductivity field Ch = dtype(0.5 c) needs the same seven
+//     neighbours but is static: its plane x travels through the same LDS
+//     exchange, and across the march only one plane of Ch and one plane of x
+//     face weights live (w- of plane x + 1 is w+ of plane x bit for bit: the
+//     add commutes), not a three-plane queue.  Ch of plane x + 1 is loaded at
+//     the top of iteration x, ahead of the barrier.
+//     HBM traffic: one read of T, one of Ch, one write (1.5x the uniform
+//     single step; 2x with a source).
+//   * stencil_var_naive: one lane per (y, z) column, fourteen loads per
+//     point; thin boxes and the test oracle.
+// One tile shape per dtype: fp64 V=2 R=4 WZ=1 WY=4, fp32 V=4 R=4 WZ=1 WY=4
+// (fewer rows per wave than the uniform kernel's default for the second
+// field's registers, four waves for its half of the 33 KiB of LDS).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "hip_helpers.hpp"
+
+namespace heat3d {
+namespace hip {
+
+template <typename Real, bool SRC>
+__global__ __launch_bounds__(256) void stencil_var_naive(const Real* __restrict__ in, Real* __restrict__ out,
+                                                         const Real* __restrict__ h,
+                                                         const Real* __restrict__ src, Layout L, Box b, Real Dx,
+                                                         Real Dy, Real Dz, unsigned long long* res,
+                                                         const int* done) {
+  if (flag_set(done)) return;
+  const int64_t k = b.lo[2] + (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const int64_t j = b.lo[1] + (int64_t)blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int64_t x0 = b.lo[0] + (int64_t)blockIdx.z * 64;
+  const int64_t x1 = min(x0 + 64, b.hi[0]);
+  double m = 0.0;
+  if (k < b.hi[2] && j < b.hi[1]) {
+    const int64_t sx = L.sx, sy = L.sy;
+    for (int64_t i = x0; i < x1; ++i) {
+      const int64_t c = L.index(i, j, k);
+      const Real T = in[c];
+      Real nv = ftcs_update_var<Real>(T, in[c - sx], in[c + sx], in[c - sy], in[c + sy], in[c - 1], in[c + 1], h[c],
+                                      h[c - sx], h[c + sx], h[c - sy], h[c + sy], h[c - 1], h[c + 1], Dx, Dy, Dz);
+      if constexpr (SRC) nv = add_source<Real>(nv, src[c]);
+      out[c] = nv;
+      m = res_max(m, resid_abs(nv, T));
+    }
+  }
+  if (res) residual_commit(res, m);
+}
+
+struct VarGeom {
+  int64_t z0a;        // first z of tile column 0 (box z0 rounded down to V)
+  int nzb, nyb, nxs;  // tiles along z, y; x segments
+  int seg;
+  int64_t nblocks;
+  int xq, xr;         // XCD remap
+  int nt;
+};
+
+template <typename Real, int V, int R, int WZ, int WY, bool SRC>
+__global__ __launch_bounds__(64 * WZ * WY) void stencil_var_tile(const Real* __restrict__ in,
+                                                                Real* __restrict__ out,
+                                                                const Real* __restrict__ hf,
+                                                                const Real* __restrict__ src, Layout L, Box b,
+                                                                VarGeom g, Real Dx, Real Dy, Real Dz,
+                                                                unsigned long long* res, const int* done) {
+  typedef typename VecOf<Real, V>::type Vec;
+  constexpr int TZ = 64 * V;
+  constexpr int NW = WZ * WY;
+  // [parity][field: T, Ch][wave][bottom/top row][lane]
+  __shared__ Vec s_rows[2][2][NW][2][64];
+  // [parity][field][wave][row][left/right]
+  __shared__ Real s_edge[2][2][NW][R][2];
+  if (flag_set(done)) return;  // uniform across the block
+
+  const int blk = blockIdx.x;
+  const int xcd = blk & 7;
+  int64_t t = xcd * g.xq + min(xcd, g.xr) + (blk >> 3);
+  const int zb = (int)(t % g.nzb);
+  t /= g.nzb;
+  const int ybk = (int)(t % g.nyb);
+  const int xs = (int)(t / g.nyb);
+
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int wz = wave % WZ, wy = wave / WZ;
+  const int64_t kb = g.z0a + ((int64_t)zb * WZ + wz) * TZ;
+  const int64_t k = kb + (int64_t)lane * V;
+  const int64_t yb = b.lo[1] + ((int64_t)ybk * WY + wy) * R;
+  const int ract = (int)max((int64_t)0, min((int64_t)R, b.hi[1] - yb));
+  // neighbours in the tile: below (wy-1) always has R rows; above only if I am full
+  const bool nb_lo = wy > 0;
+  const bool nb_hi = (wy + 1 < WY) && (ract == R) && (yb + R < b.hi[1]);
+  const bool nb_left = wz > 0, nb_right = wz + 1 < WZ;
+  const int64_t xa = b.lo[0] + (int64_t)xs * g.seg;
+  const int64_t xe = min(xa + (int64_t)g.seg, b.hi[0]);
+  const int64_t sx = L.sx, sy = L.sy;
+
+  bool valid[V];
+  bool allvalid = true;
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    valid[v] = (k + v >= b.lo[2]) && (k + v < b.hi[2]);
+    allvalid &= valid[v];
+  }
+  const int64_t base0 = L.index(0, yb, k);
+  // outer-edge gather: lanes [0,R) left edges (only the wz == 0 wave), lanes
+  // [32,32+R) right edges (only the wz == WZ-1 wave)
+  const int er = lane < 32 ? lane : lane - 32;
+  const bool eload = er < ract && (lane < 32 ? !nb_left : !nb_right);
+  const int64_t ebase = L.index(0, yb + er, lane < 32 ? kb - 1 : kb + TZ);
+
+  auto ld = [&](const Real* f, int64_t plane, int r) -> Vec {
+    return *reinterpret_cast<const Vec*>(f + base0 + plane * sx + (int64_t)r * sy);
+  };
+
+  Vec qm[R], qc[R], qp[R];  // T planes x-1, x, x+1
+  Vec hc[R], wx[R];         // Ch plane x; face weights between planes x-1 and x
+#pragma unroll
+  for (int r = 0; r < R; ++r)
+    if (r < ract) {
+      qm[r] = ld(in, xa - 1, r);
+      qc[r] = ld(in, xa, r);
+      qp[r] = ld(in, xa + 1, r);
+      hc[r] = ld(hf, xa, r);
+      const Vec hm = ld(hf, xa - 1, r);
+#pragma unroll
+      for (int v = 0; v < V; ++v) wx[r][v] = hc[r][v] + hm[v];
+    }
+  Vec hb = {}, ht = {}, gb = {}, gt = {};  // outer halo rows of T and of Ch, plane x
+  if (ract > 0 && !nb_lo) {
+    hb = ld(in, xa, -1);
+    gb = ld(hf, xa, -1);
+  }
+  if (ract > 0 && !nb_hi) {
+    ht = ld(in, xa, ract);
+    gt = ld(hf, xa, ract);
+  }
+  Real ed = eload ? in[ebase + xa * sx] : Real(0);
+  Real eg = eload ? hf[ebase + xa * sx] : Real(0);
+
+  double m = 0.0;
+  int par = 0;
+  for (int64_t x = xa; x < xe; ++x) {
+    // publish this wave's boundary rows / edge points of plane x, T and Ch
+    if (ract > 0) {
+      s_rows[par][0][wave][0][lane] = qc[0];
+      s_rows[par][1][wave][0][lane] = hc[0];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (r == ract - 1) {  // static register index
+          s_rows[par][0][wave][1][lane] = qc[r];
+          s_rows[par][1][wave][1][lane] = hc[r];
+        }
+        if (r < ract) {
+          if (lane == 0) {
+            s_edge[par][0][wave][r][0] = qc[r][0];
+            s_edge[par][1][wave][r][0] = hc[r][0];
+          }
+          if (lane == 63) {
+            s_edge[par][0][wave][r][1] = qc[r][V - 1];
+            s_edge[par][1][wave][r][1] = hc[r][V - 1];
+          }
+        }
+      }
+    }
+    // Ch of plane x+1 (this plane's w+); prefetch T plane x+2 and the outer
+    // halo of plane x+1
+    Vec hn[R], qn[R];
+    Vec hbn = {}, htn = {}, gbn = {}, gtn = {};
+    Real edn = Real(0), egn = Real(0);
+    const bool more = x + 1 < xe;
+    if (ract > 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r)
+        if (r < ract) hn[r] = ld(hf, x + 1, r);
+      if (more) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+          if (r < ract) qn[r] = ld(in, x + 2, r);
+        if (!nb_lo) {
+          hbn = ld(in, x + 1, -1);
+          gbn = ld(hf, x + 1, -1);
+        }
+        if (!nb_hi) {
+          htn = ld(in, x + 1, ract);
+          gtn = ld(hf, x + 1, ract);
+        }
+        if (eload) {
+          edn = in[ebase + (x + 1) * sx];
+          egn = hf[ebase + (x + 1) * sx];
+        }
+      }
+    }
+    __syncthreads();
+    if (ract > 0) {
+      const Vec ylo = nb_lo ? s_rows[par][0][wave - WZ][1][lane] : hb;
+      const Vec yhi = nb_hi ? s_rows[par][0][wave + WZ][0][lane] : ht;
+      const Vec glo = nb_lo ? s_rows[par][1][wave - WZ][1][lane] : gb;
+      const Vec ghi = nb_hi ? s_rows[par][1][wave + WZ][0][lane] : gt;
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (r < ract) {
+          const Vec c = qc[r], h = hc[r];
+          Vec sv = {};
+          if constexpr (SRC) sv = *reinterpret_cast<const Vec*>(src + base0 + x * sx + (int64_t)r * sy);
+          const Vec ym = r == 0 ? ylo : qc[r > 0 ? r - 1 : 0];
+          const Vec yp = (r == ract - 1) ? yhi : qc[r + 1 < R ? r + 1 : R - 1];
+          const Vec gm = r == 0 ? glo : hc[r > 0 ? r - 1 : 0];
+          const Vec gp = (r == ract - 1) ? ghi : hc[r + 1 < R ? r + 1 : R - 1];
+          const Real left = nb_left ? s_edge[par][0][wave - 1][r][1] : readlane(ed, r);
+          const Real right = nb_right ? s_edge[par][0][wave + 1][r][0] : readlane(ed, 32 + r);
+          const Real hleft = nb_left ? s_edge[par][1][wave - 1][r][1] : readlane(eg, r);
+          const Real hright = nb_right ? s_edge[par][1][wave + 1][r][0] : readlane(eg, 32 + r);
+          Vec zm, zp, hzm, hzp, wxp, nv;
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            zm[v] = v == 0 ? dpp_shr1(left, c[V - 1]) : c[v > 0 ? v - 1 : 0];
+            zp[v] = v == V - 1 ? dpp_shl1(right, c[0]) : c[v + 1 < V ? v + 1 : 0];
+            hzm[v] = v == 0 ? dpp_shr1(hleft, h[V - 1]) : h[v > 0 ? v - 1 : 0];
+            hzp[v] = v == V - 1 ? dpp_shl1(hright, h[0]) : h[v + 1 < V ? v + 1 : 0];
+          }
+#pragma unroll
+          for (int v = 0; v < V; ++v) {
+            wxp[v] = h[v] + hn[r][v];
+            nv[v] = ftcs_update_varw<Real>(c[v], qm[r][v], qp[r][v], ym[v], yp[v], zm[v], zp[v], wx[r][v], wxp[v],
+                                           h[v] + gm[v], h[v] + gp[v], h[v] + hzm[v], h[v] + hzp[v], Dx, Dy, Dz);
+            if constexpr (SRC) nv[v] = add_source<Real>(nv[v], sv[v]);
+            if (valid[v]) m = res_max(m, resid_abs(nv[v], c[v]));
+          }
+          wx[r] = wxp;  // w- of plane x+1
+          Real* dst = out + base0 + x * sx + (int64_t)r * sy;
+          if (allvalid) {
+            if (g.nt) __builtin_nontemporal_store(nv, reinterpret_cast<Vec*>(dst));
+            else *reinterpret_cast<Vec*>(dst) = nv;
+          } else {
+#pragma unroll
+            for (int v = 0; v < V; ++v)
+              if (valid[v]) dst[v] = nv[v];
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      qm[r] = qc[r];
+      qc[r] = qp[r];
+      qp[r] = qn[r];
+      hc[r] = hn[r];
+    }
+    hb = hbn;
+    ht = htn;
+    gb = gbn;
+    gt = gtn;
+    ed = edn;
+    eg = egn;
+    par ^= 1;
+  }
+  if (res) residual_commit(res, m);
+}
+
+template <typename Real, bool SRC>
+static void launch_var_naive(const StencilParams& p, hipStream_t s) {
+  const Box& b = p.box;
+  dim3 grid((unsigned)((b.extent(2) + 63) / 64), (unsigned)((b.extent(1) + 3) / 4),
+            (unsigned)((b.extent(0) + 63) / 64));
+  unsigned long long* res = p.state && p.residual ? &p.state->residual[p.slot] : nullptr;
+  const int* done = p.state ? &p.state->done : nullptr;
+  hipLaunchKernelGGL((stencil_var_naive<Real, SRC>), grid, dim3(256), 0, s, static_cast<const Real*>(p.in),
+                     static_cast<Real*>(p.out), static_cast<const Real*>(p.cond), static_cast<const Real*>(p.src),
+                     p.L, b, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], res, done);
+  HIPK_CHECK(hipGetLastError());
+}
+
+template <typename Real, int V, int R, int WZ, int WY, bool SRC>
+static void launch_var_tile(const StencilParams& p, const KernelSpec& k, hipStream_t s) {
+  const Box& b = p.box;
+  constexpr int TZ = 64 * V;
+  VarGeom g;
+  g.nt = k.NT;
+  g.z0a = (b.lo[2] / V) * V;
+  const int64_t nzt = (b.hi[2] - g.z0a + TZ - 1) / TZ;
+  g.nzb = (int)((nzt + WZ - 1) / WZ);
+  g.nyb = (int)((b.extent(1) + (int64_t)R * WY - 1) / ((int64_t)R * WY));
+  int seg = k.L;
+  if (seg <= 0) {
+    static const int slots =
+        device_slots(reinterpret_cast<const void*>(&stencil_var_tile<Real, V, R, WZ, WY, SRC>), 64 * WZ * WY);
+    seg = choose_segment(b.extent(0), (int64_t)g.nzb * g.nyb, slots);
+  }
+  g.seg = (int)std::min<int64_t>(seg, std::max<int64_t>(1, b.extent(0)));
+  g.nxs = (int)((b.extent(0) + g.seg - 1) / g.seg);
+  g.nblocks = (int64_t)g.nzb * g.nyb * g.nxs;
+  HEAT3D_CHECK(g.nblocks < (1LL << 31), "too many blocks");
+  g.xq = (int)(g.nblocks / 8);
+  g.xr = (int)(g.nblocks % 8);
+  unsigned long long* res = p.state && p.residual ? &p.state->residual[p.slot] : nullptr;
+  const int* done = p.state ? &p.state->done : nullptr;
+  hipLaunchKernelGGL((stencil_var_tile<Real, V, R, WZ, WY, SRC>), dim3((unsigned)g.nblocks), dim3(64 * WZ * WY), 0,
+                     s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out),
+                     static_cast<const Real*>(p.cond), static_cast<const Real*>(p.src), p.L, b, g, (Real)p.D[0],
+                     (Real)p.D[1], (Real)p.D[2], res, done);
+  HIPK_CHECK(hipGetLastError());
+}
+
+template <typename Real, bool SRC>
+static void dispatch_var(const StencilParams& p, const KernelSpec& k, hipStream_t s) {
+  // thin boxes as in the uniform dispatch (dispatch_tile)
+  if (k.kind == KernelSpec::Naive || p.box.extent(2) < 32 || p.box.extent(1) < 2)
+    return launch_var_naive<Real, SRC>(p, s);
+  // (the spec's tile-shape fields belong to the uniform kernel; L and the
+  // store policy apply)
+  if constexpr (sizeof(Real) == 8) launch_var_tile<Real, 2, 4, 1, 4, SRC>(p, k, s);
+  else launch_var_tile<Real, 4, 4, 1, 4, SRC>(p, k, s);
+}
+
+void stencil_var(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
+  if (p.box.empty()) return;
+  HEAT3D_CHECK(p.cond, "stencil_var needs a conductivity field");
+  HEAT3D_CHECK(k.kind == KernelSpec::Naive || k.kind == KernelSpec::Tile, "single-step kernels: naive | tile");
+  if (t == DType::F64) {
+    if (p.src) dispatch_var<double, true>(p, k, S(stream));
+    else dispatch_var<double, false>(p, k, S(stream));
+  } else {
+    if (p.src) dispatch_var<float, true>(p, k, S(stream));
+    else dispatch_var<float, false>(p, k, S(stream));
+  }
+}
+
+}  // namespace hip
+}  // namespace heat3d

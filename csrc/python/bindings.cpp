@@ -456,13 +456,14 @@ PYBIND11_MODULE(_heat3d, m) {
   py::module_ hk = m.def_submodule("hip", "gfx950 kernels on device pointers");
   hk.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
-                       const std::string& kernel, int64_t stream, int64_t src_ptr) {
+                       const std::string& kernel, int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     hip::stencil(t, p, KernelSpec::parse(kernel), reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
-     py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"), py::arg("src_ptr") = 0);
+     py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   hk.def("stencil2", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                         std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                         int64_t stream) {
@@ -481,25 +482,26 @@ PYBIND11_MODULE(_heat3d, m) {
   hk.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                             int64_t stream, int64_t src_ptr) {
+                             int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), gx);
     p.ux[0] = ux[0];
     p.ux[1] = ux[1];
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("gx"), py::arg("box"),
      py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
-     py::arg("src_ptr") = 0);
+     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   // deep ghosts on every axis (block decompositions): g = (gx, gy, gz),
   // u = update ranges (ux0, ux1, uy0, uy1, uz0, uz1)
   hk.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                              int64_t stream, int64_t src_ptr) {
+                              int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -509,12 +511,13 @@ PYBIND11_MODULE(_heat3d, m) {
       p.uz[e] = u[4 + e];
     }
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
-     py::arg("src_ptr") = 0);
+     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   hk.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h, int64_t stream) {
     DType t = dt_of(dt);
@@ -551,35 +554,37 @@ PYBIND11_MODULE(_heat3d, m) {
   py::module_ ck = m.def_submodule("cpu", "OpenMP host kernels on host pointers");
   ck.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
-                       int64_t src_ptr) {
+                       int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     py::gil_scoped_release nogil;
     cpu::stencil(t, p);
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
-     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0);
+     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   ck.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                             int64_t src_ptr) {
+                             int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), gx);
     p.ux[0] = ux[0];
     p.ux[1] = ux[1];
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
     py::gil_scoped_release nogil;
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("gx"), py::arg("box"),
-     py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0);
+     py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   ck.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                              int64_t src_ptr) {
+                              int64_t src_ptr, int64_t cond_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -589,13 +594,14 @@ PYBIND11_MODULE(_heat3d, m) {
       p.uz[e] = u[4 + e];
     }
     p.src = reinterpret_cast<const void*>(src_ptr);
+    p.cond = reinterpret_cast<const void*>(cond_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
     py::gil_scoped_release nogil;
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
-     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0);
+     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
   ck.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h) {
     DType t = dt_of(dt);
@@ -754,6 +760,21 @@ PYBIND11_MODULE(_heat3d, m) {
         py::gil_scoped_release nogil;
         s.set_field(d);
       })
+      // relative conductivity c in (0, 1] (global array); values are checked by the solver
+      .def("set_conductivity", [](Solver& s, py::array_t<double, py::array::c_style | py::array::forcecast> c) {
+        const auto& N = s.decomposition().N;
+        if ((int64_t)c.size() != N[0] * N[1] * N[2])
+          throw UsageError("set_conductivity: array size does not match the grid");
+        const double* d = c.data();
+        py::gil_scoped_release nogil;
+        s.set_conductivity(d);
+      })
+      .def("clear_conductivity", [](Solver& s) {
+        py::gil_scoped_release nogil;
+        s.clear_conductivity();
+      })
+      .def_property_readonly("has_conductivity", &Solver::has_conductivity)
+      .def_property_readonly("sweeps_active", &Solver::sweeps_active)
       .def_property_readonly("has_source", &Solver::has_source)
       .def("inject", &Solver::inject, py::arg("idx"), py::arg("i"), py::arg("j"), py::arg("k"),
            py::arg("value"), py::arg("previous") = false)

@@ -432,6 +432,7 @@ Solver::~Solver() {
     for (auto* f : l.field)
       if (f) be_->release(f);
     if (l.source) be_->release(l.source);
+    if (l.cond) be_->release(l.cond);
     for (auto& io : l.faces) {
       be_->release(io.sendbuf);
       be_->release(io.recvbuf);
@@ -486,12 +487,16 @@ void Solver::preflight_source() {
   std::size_t extra = 0;
   for (const auto& l : local_)
     if (!l.source) extra += l.L.bytes();
+  preflight_extra_field("heat source", extra);
+}
+
+void Solver::preflight_extra_field(const char* what, std::size_t extra) {
   std::size_t free_now = 0, total = 0;
   const bool known = be_->mem_info(&free_now, &total);
   if (known && cfg_.mem_preflight) {
     const double reserve = cfg_.mem_reserve_gb * 1e9;
     if ((double)extra + reserve > (double)free_now)
-      HEAT3D_THROW("memory preflight: the heat source needs " << extra / 1e9 << " GB more on this "
+      HEAT3D_THROW("memory preflight: the " << what << " needs " << extra / 1e9 << " GB more on this "
                    << (be_->is_gpu() ? "GPU" : "host") << " (one more field per local subdomain) plus a "
                    << reserve / 1e9 << " GB reserve, but only " << free_now / 1e9 << " of " << total / 1e9
                    << " GB are free");
@@ -619,6 +624,8 @@ void Solver::retune() {
   }
   rl_ = false;
   for (bool& b : rl_d_) b = false;
+  // a conductivity field: single steps only, nothing to time
+  if (has_cond_) return;
   tune_schedules();
   calibrate_remainders();
   // the sweep form is final: its last-residual variant, where one exists
@@ -719,7 +726,7 @@ void Solver::canary_stream_graphs() {
     sg_state_ = "unverified";
     return;
   }
-  const int64_t cyc = tb_ ? (int64_t)K_ * (nbuf_ == 3 ? 6 : 2) : (nbuf_ == 3 ? 6 : 2);
+  const int64_t cyc = sweeping() ? (int64_t)K_ * (nbuf_ == 3 ? 6 : 2) : (nbuf_ == 3 ? 6 : 2);
   const int G = graph_len_for(cyc);
   if (G <= 0) {
     sg_state_ = "unverified";
@@ -865,6 +872,7 @@ void Solver::tune_schedules() {
       sp.out = l.field[nxt(0)];
       sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
       sp.box = box;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
@@ -968,6 +976,7 @@ void Solver::calibrate_remainders() {
       sp.out = l.field[nxt(0)];
       sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
       sp.cu_reserved = be_->reserved_cus();
@@ -1183,7 +1192,7 @@ double Solver::link_probe(std::size_t bytes, int reps) {
 }
 
 int Solver::preheat(int sweeps) {
-  if (!tb_ || sweeps <= 0) return 0;
+  if (!sweeping() || sweeps <= 0) return 0;
   // Ordered behind every issued sweep and convergence check (join_pipeline),
   // the warm-up sweeps carry the device done flag without residual slots
   // (StencilParams::residual = false): once any issued iteration has met the
@@ -1202,6 +1211,7 @@ int Solver::preheat(int sweeps) {
       sp.out = l.field[nxt(cur())];
       sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
       sp.box = l.tb_interior;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = dstate_;
@@ -1299,6 +1309,7 @@ void Solver::enqueue_iteration(int p, int bi) {
     sp.out = l.field[nxt(bi)];
     sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1383,6 +1394,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
   const bool lb = dv || (thick && long_halo_);
   H3D_TRACE("sweep" << Kp << " issued=" << issued_ << " buf=" << bi << (capturing_ ? " (capturing)" : ""));
   HEAT3D_CHECK(tb_, "temporal blocking not enabled for this decomposition");
+  HEAT3D_CHECK(!has_cond_, "K-step sweeps have no conductivity form");
   if (last_kind_ != 2) join_pipeline();
   last_kind_ = 2;
   // lagged schedule: events and residual slots alternate by sweep parity
@@ -1408,6 +1420,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
     sp.out = l.field[nxt(bi)];
     sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1588,6 +1601,7 @@ void Solver::resolve_coarse() {
       sp.out = l.field[nxt(hit->inbuf)];  // rewritten with the values it holds
       sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
       sp.box = b;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = rstate_;
@@ -1674,7 +1688,7 @@ void Solver::prof_record(int sweep, int id, StreamId s) {
 
 std::vector<std::pair<std::string, double>> Solver::profile_sweeps(int n) {
   std::vector<std::pair<std::string, double>> out;
-  if (!tb_ || n < 3) return out;
+  if (!sweeping() || n < 3) return out;
   flush_pending_reduce();
   const std::size_t need = (std::size_t)n * PE_COUNT;
   while (prof_ev_.size() < need) prof_ev_.push_back(be_->event_create());
@@ -1795,6 +1809,7 @@ void Solver::finalize_converged(int64_t c) {
         sp.out = l.field[dst];
         sp.L = l.L;
     sp.src = l.source;
+    sp.cond = l.cond;
         sp.box = l.owned;
         const int64_t w = m - j;
         for (int a = 0; a < 3; ++a) {
@@ -1833,7 +1848,7 @@ void Solver::accumulate_phase_times() {
 // event / residual-slot parity of single steps (2) and of overlapped sweeps (2).
 int Solver::graph_len_for(int64_t n) const {
   int cyc;
-  if (tb_) cyc = K_ * (nbuf_ == 3 ? 6 : 2);
+  if (sweeping()) cyc = K_ * (nbuf_ == 3 ? 6 : 2);
   else cyc = nbuf_ == 3 ? 6 : 2;
   // auto: 32 iterations, 96 for the overlapped multi-stream schedule, whose
   // per-stream graphs start and end joined (each launch drains the halo /
@@ -1845,12 +1860,12 @@ int Solver::graph_len_for(int64_t n) const {
   // a step count shorter than one cycle (the driver's 20-step window at 8
   // ranks: 12 steps in K = 3 sweeps + 2 long sweeps; the 3-buffer cycle is
   // 18) is one graph too, replayable only from the same state
-  if (G == 0 && tb_) G = (int)(n - n % K_);
+  if (G == 0 && sweeping()) G = (int)(n - n % K_);
   return G;
 }
 
 int Solver::long_sweeps_for(int64_t n) const {
-  if (!tb_ || (has_halo_ && !long_halo_) || !kspec2_.multi_step()) return 0;
+  if (!sweeping() || (has_halo_ && !long_halo_) || !kspec2_.multi_step()) return 0;
   if (K_ + 1 > 6 || K_ + 1 > kResidualSlots) return 0;
   if (long_major_ && cfg_.long_sweeps) {
     // the most long sweeps b with n - b (K + 1) a multiple of K (b = n mod K
@@ -1898,7 +1913,7 @@ bool Solver::stream_graphs_enabled() const {
 }
 
 Solver::GraphEntry* Solver::find_graph(int G, int kind_req) {
-  const int kind = kind_req ? kind_req : tb_ ? 2 : 1;
+  const int kind = kind_req ? kind_req : sweeping() ? 2 : 1;
   for (auto& g : graphs_)
     if (g.exec && g.G == G && g.kind == kind && g.buf == cur() && g.parity == (int)(issued_ & 1) &&
         g.sparity == (int)(nsweep_ & 1) && g.first == (issued_ == 0))
@@ -1925,7 +1940,7 @@ Solver::GraphEntry* Solver::build_graph(int G, int kind_req) {
   join_pipeline();
   GraphEntry e;
   e.G = G;
-  e.kind = kind_req ? kind_req : tb_ ? 2 : 1;  // 3: K+1-step sweeps (long-major)
+  e.kind = kind_req ? kind_req : sweeping() ? 2 : 1;  // 3: K+1-step sweeps (long-major)
   e.buf = cur();
   e.parity = (int)(issued_ & 1);
   e.sparity = (int)(nsweep_ & 1);
@@ -2073,7 +2088,7 @@ void Solver::run_chunk(int64_t n) {
         continue;
       }
     }
-    if (tb_ && n >= 2 && !phase_timing_) {
+    if (sweeping() && n >= 2 && !phase_timing_) {
       // a full sweep, or a partial one for a remainder of 2 .. K-1 steps
       const int Kp = (int)std::min<int64_t>(n, K_);
       record_segment(issued_, Kp, cur());
@@ -2162,7 +2177,7 @@ RunResult Solver::run() {
   // back to single steps; with graphs at least one whole graph, whose launch
   // joins the streams (the overlapped schedule drains its pipeline there)
   int64_t K = std::max(1, cfg_.check_every);
-  if (tb_) {
+  if (sweeping()) {
     // long-major: chunks of whole K+1-step sweeps too (24 = 6 x 4)
     const int64_t cyc = (int64_t)K_ * (nbuf_ == 3 ? 6 : 2) * (long_major_ ? K_ + 1 : 1);
     if (graphs_allowed()) K = std::max<int64_t>(K, graph_len_for(INT32_MAX));

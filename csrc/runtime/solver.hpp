@@ -82,7 +82,7 @@ class Solver {
   int64_t interior_points() const { return (dec_.N[0] - 2) * (dec_.N[1] - 2) * (dec_.N[2] - 2); }
   std::string kernel_name() const {
     const std::string one = kspec_.resolved(cfg_.dtype).str();
-    return tb_ ? kspec2_.resolved(cfg_.dtype).str() + "+" + one : one;
+    return sweeping() ? kspec2_.resolved(cfg_.dtype).str() + "+" + one : one;
   }
 
   // (Re)initialise fields: analytic IC/BC (heat3D.cu:408-453) or restart.
@@ -137,6 +137,23 @@ class Solver {
   // N0*N1*N2 values in the checkpoint field file's order; every rank reads
   // only its own box; a wrong file size is a UsageError
   void set_source_file(const std::string& path);
+  // Spatially varying conductivity, T_t = div(kappa grad T) + q with
+  // kappa = alpha * c: `global_c` is the relative conductivity on the global
+  // vertex grid (same shape and order as the source), every value finite and
+  // in (0, 1], else every rank throws UsageError.  Each local rank keeps
+  // Ch = dtype(0.5 * c) on its owned box plus its full ghost depth, the wall
+  // vertices included (a face weight towards a wall reads c there).  While a
+  // conductivity is set every iteration runs as a single step (the K-step
+  // sweep kernels have no conductivity form); the deep ghosts and their
+  // exchange stay.  Setting or clearing behaves like set_source: graphs are
+  // destroyed, the convergence state returns to iteration 0, the field is
+  // kept.  Not with --compat.
+  void set_conductivity(const double* global_c);
+  void set_conductivity_file(const std::string& path);
+  void clear_conductivity();
+  bool has_conductivity() const { return has_cond_; }
+  // K-step sweeps are what run() / step() issue (temporal blocking on, no conductivity field)
+  bool sweeps_active() const { return sweeping(); }
   void set_field_file(const std::string& path);
 
   // Error vs analytic steady state (heat3D.cu:1093-1106, with a true global
@@ -250,6 +267,7 @@ class Solver {
     Layout L;
     void* field[3] = {nullptr, nullptr, nullptr};  // nbuf_ of them in use
     void* source = nullptr;  // S = dtype(dt * q) in layout L, allocated by set_source
+    void* cond = nullptr;    // Ch = dtype(0.5 * c) in layout L, allocated by set_conductivity
     Box owned, interior;
     std::vector<Box> shell;
     std::vector<FaceIO> faces;
@@ -275,12 +293,17 @@ class Solver {
   bool has_source_ = false;
   bool initialized_ = false;
   void preflight_source();
+  bool has_cond_ = false;
+  // K-step sweeps run (temporal blocking on and no conductivity field)
+  bool sweeping() const { return tb_ && !has_cond_; }
+  void preflight_extra_field(const char* what, std::size_t extra);
   // copies n values of global row (gi, gj) from column gk on
   using GlobalRows = std::function<void(int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst)>;
   GlobalRows rows_of_array(const double* g) const;
   GlobalRows rows_of_file(int fd) const;
   void set_source_rows(const GlobalRows& rows);
   void set_field_rows(const GlobalRows& rows);
+  void set_conductivity_rows(const GlobalRows& rows);
   void scatter_global(const GlobalRows& rows, double scale, const Local& l, void* const* bufs, int nbufs);
   void consolidate_fields();
   // Start-up canary of the per-stream graphs (initialize(), every rank at the
@@ -344,7 +367,7 @@ class Solver {
   // is not a multiple of K (single subdomain, lean kernel): n = a K + b (K+1)
   // costs a + b HBM passes where a K-sweep + a partial one would cost one more.
   int long_sweeps_for(int64_t n) const;
-  bool multi_stream() const { return tb_ ? tb_overlap_ : overlap_; }
+  bool multi_stream() const { return sweeping() ? tb_overlap_ : overlap_; }
   // buffer holding T^{issued_}; a step or a K-step sweep reads cur() and
   // writes nxt(cur())
   int cur() const { return cur_; }

@@ -409,6 +409,8 @@ void Solver::save_checkpoint(const std::string& dir) {
     j.set("layout", std::string("global z-fastest, N0*N1*N2 values"));
     // the source itself is not written: the caller sets it again before a restart
     j.set_raw("has_source", has_source_ ? "true" : "false");
+    // nor the conductivity field
+    j.set_raw("has_conductivity", has_cond_ ? "true" : "false");
     io::write_file_atomic(dir + "/meta.json", j.dump() + "\n");
     // older field files, and the temp files of saves that a crash
     // interrupted (a full-grid field.<iter>.raw.tmp each)
@@ -436,6 +438,9 @@ void Solver::load_checkpoint(const std::string& dir) {
   HEAT3D_CHECK(!(meta.count("has_source") && meta["has_source"] == "true") || has_source_,
                "checkpoint " << dir << " was written with a heat source, which is not stored in it: set the source "
                                        "again (set_source / --source) before loading it");
+  HEAT3D_CHECK(!(meta.count("has_conductivity") && meta["has_conductivity"] == "true") || has_cond_,
+               "checkpoint " << dir << " was written with a conductivity field, which is not stored in it: set it "
+                                       "again (set_conductivity / --conductivity) before loading it");
   const int64_t it = std::atoll(meta["iteration"].c_str());
   const double norm = std::atof(meta["norm"].c_str());
   const int64_t* N = dec_.N;
@@ -645,6 +650,75 @@ void Solver::clear_source() {
   if (!initialized_) return;
   consolidate_fields();
   retune();
+  reset_state(false);
+}
+
+void Solver::set_conductivity_file(const std::string& path) {
+  const int fd = open_global_file(path, dec_.N, "--conductivity");
+  try {
+    set_conductivity_rows(rows_of_file(fd));
+  } catch (...) {
+    io::close_raw(fd);
+    throw;
+  }
+  io::close_raw(fd);
+}
+
+void Solver::set_conductivity(const double* global_c) { set_conductivity_rows(rows_of_array(global_c)); }
+
+void Solver::set_conductivity_rows(const GlobalRows& rows) {
+  if (cfg_.compat) throw UsageError("a conductivity field is not part of --compat (the reference's uniform material)");
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  std::size_t extra = 0;
+  for (const auto& l : local_)
+    if (!l.cond) extra += l.L.bytes();
+  preflight_extra_field("conductivity field", extra);
+  // every value this process reads (its boxes and their ghost depth, the
+  // wall vertices included) must be finite and in (0, 1]
+  unsigned long long bad = 0;
+  const GlobalRows checked = [&rows, &bad](int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst) {
+    rows(gi, gj, gk, n, dst);
+    for (int64_t k = 0; k < n; ++k) bad += !(dst[k] > 0.0 && dst[k] <= 1.0);  // NaN fails both
+  };
+  for (auto& l : local_) {
+    if (!l.cond) l.cond = be_->alloc(l.L.bytes());
+    void* bufs[1] = {l.cond};
+    // Ch = dtype(0.5 * c): the product in double, rounded once
+    scatter_global(checked, 0.5, l, bufs, 1);
+  }
+  // one decision for the job: no rank throws alone while its peers go on
+  bad = allreduce_sum_u64(bad);
+  if (bad) {
+    has_cond_ = true;  // (the buffers exist)
+    clear_conductivity();
+    throw UsageError("conductivity: " + std::to_string(bad) +
+                     " value(s) are not finite and in (0, 1] (relative conductivity c = kappa / alpha; the time "
+                     "step is that of the best-conducting material); no conductivity field is set");
+  }
+  has_cond_ = true;
+  if (!initialized_) return;
+  consolidate_fields();
+  retune();
+  reset_state(false);
+}
+
+void Solver::clear_conductivity() {
+  if (!has_cond_) return;
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  for (auto& l : local_) {
+    if (!l.cond) continue;
+    planned_bytes_ -= std::min(planned_bytes_, l.L.bytes());
+    be_->release(l.cond);
+    l.cond = nullptr;
+  }
+  has_cond_ = false;
+  if (!initialized_) return;
+  consolidate_fields();
+  retune();  // the K-step sweeps are back: timed as at initialize()
   reset_state(false);
 }
 

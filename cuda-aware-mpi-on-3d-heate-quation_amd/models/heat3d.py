@@ -78,6 +78,30 @@ class HeatEquation3D:
         sx, sy, sz = (np.sin(np.pi * np.arange(n, dtype=np.float64) * hd) for n, hd in zip(self.n, h))
         return (self.alpha * lam * float(amplitude)) * sx[:, None, None] * sy[None, :, None] * sz[None, None, :]
 
+    def layered_conductivity(self, c_low: float, c_high: float, split: float = 0.5) -> np.ndarray:
+        """Two-layer body: relative conductivity c = ``c_low`` where y_j < ``split``,
+        ``c_high`` elsewhere (global array, 0 < c <= 1)."""
+        y = np.arange(self.n[1], dtype=np.float64) * self.h[1]
+        c = np.where(y < float(split), float(c_low), float(c_high))
+        return np.broadcast_to(c[None, :, None], self.n).copy()
+
+    def layered_steady(self, c: np.ndarray) -> np.ndarray:
+        """Exact steady state of the discrete scheme for a conductivity that
+        varies in y only, between the walls T(y=0) = 0 and T(y=1) = 1: a
+        constant flux w_m (p_{m+1} - p_m) through every y face, w_m the face
+        mean 0.5 (c_m + c_{m+1}), so p_0 = 0 and
+        p_j = (sum_{m<j} 1/w_m) / (sum_{m<N-1} 1/w_m); constant in x and z."""
+        c = np.asarray(c, dtype=np.float64)
+        if c.shape != tuple(self.n):
+            raise ValueError(f"layered_steady: shape {c.shape} != grid {tuple(self.n)}")
+        cy = c[0, :, 0]
+        if not np.array_equal(c, np.broadcast_to(cy[None, :, None], self.n)):
+            raise ValueError("layered_steady: the conductivity must vary in y only")
+        w = 0.5 * (cy[:-1] + cy[1:])
+        r = np.concatenate(([0.0], np.cumsum(1.0 / w)))
+        p = r / r[-1]
+        return np.broadcast_to(p[None, :, None], self.n).copy()
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -222,6 +246,25 @@ class HeatSolver:
 
     def clear_source(self) -> None:
         self._s.clear_source()
+
+    def set_conductivity(self, c) -> None:
+        """Spatially varying conductivity: T_t = div(alpha c grad T) + q, ``c`` the
+        relative conductivity on the global vertex grid, 0 < c <= 1 (alpha is the
+        diffusivity of the best-conducting material, so the time step stays
+        stable).  A value outside (0, 1] or not finite is the native
+        ``UsageError`` (a RuntimeError), raised on every rank.  While set, every
+        iteration runs as a single step: the K-step sweep kernels have no
+        conductivity form.  Keeps the field, restarts the iteration count and
+        the convergence state at 0.  Collective."""
+        c = np.ascontiguousarray(np.asarray(c, dtype=np.float64))
+        if c.shape != tuple(self.model.n):
+            raise ValueError(f"set_conductivity: shape {c.shape} != grid {tuple(self.model.n)}")
+        self._ensure()
+        self._s.set_conductivity(c)
+
+    def clear_conductivity(self) -> None:
+        """Back to the uniform material (and the K-step sweeps)."""
+        self._s.clear_conductivity()
 
     def set_field(self, T) -> None:
         """User initial condition with its Dirichlet data: the boundary vertices

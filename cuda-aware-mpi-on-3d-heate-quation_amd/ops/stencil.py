@@ -84,14 +84,30 @@ def _source_ptr(src: PaddedField, source: Optional[PaddedField]) -> int:
     return source.data_ptr()
 
 
+def _cond_ptr(src: PaddedField, conductivity: Optional[PaddedField]) -> int:
+    """Pointer of the conductivity field Ch = dtype(0.5 * c) (0: uniform
+    material); same layout, dtype and device as the field."""
+    if conductivity is None:
+        return 0
+    if conductivity.layout != src.layout or conductivity.dtype != src.dtype or conductivity.device != src.device:
+        raise ValueError("the conductivity field must share the field's layout, dtype and device")
+    return conductivity.data_ptr()
+
+
 def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
               box: Optional[Sequence[int]] = None, kernel: str = "auto",
               state: Optional[torch.Tensor] = None, slot: int = 0,
-              source: Optional[PaddedField] = None) -> None:
+              source: Optional[PaddedField] = None,
+              conductivity: Optional[PaddedField] = None) -> None:
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
 
     ``source``: optional field S = dtype(dt * q) in the same layout, added to
     every updated point (kernels.hpp ftcs_update_src).
+
+    ``conductivity``: optional field Ch = dtype(0.5 * c), c the relative
+    conductivity in (0, 1], in the same layout with its ghost shell filled
+    (a face weight towards a ghost point reads Ch there): the update becomes
+    kernels.hpp ftcs_update_var (its own gfx950 kernels, stencil_var.hip).
 
     ``state``: optional uint8/int64 tensor of ``DEVICE_STATE_BYTES`` that
     receives the fused max-residual (IEEE bits of a double in its first
@@ -111,11 +127,12 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
         sptr = state.data_ptr()
     ext = native()
     qptr = _source_ptr(src, source)
+    cptr = _cond_ptr(src, conductivity)
     if src.device.type == "cuda":
         ext.hip.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot,
-                        kernel, _stream_ptr(src.flat), qptr)
+                        kernel, _stream_ptr(src.flat), qptr, cptr)
     else:
-        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr)
+        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr)
 
 
 def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: str = "auto",
@@ -143,13 +160,16 @@ def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: s
 
 def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int],
           ux: Sequence[int] = (0, -1), kernel: str = "tl3", state: Optional[torch.Tensor] = None,
-          slot: int = 0, source: Optional[PaddedField] = None) -> None:
+          slot: int = 0, source: Optional[PaddedField] = None,
+          conductivity: Optional[PaddedField] = None) -> None:
     """One K-step sweep (K from ``kernel``: tl2..tl6) on ``box``
     = (x0, x1, y0, y1, z0, z1) of a deep-ghost field, with the intermediate
     steps computed on the x range ``ux`` (the solver's x-slab schedule).
     GPU tensors run the gfx950 kernel, CPU tensors the K-single-steps
     definition (csrc/kernels/kernels_cpu.cpp).  ``source``: optional heat-source
-    field S in the same layout, added at every step."""
+    field S in the same layout, added at every step.  ``conductivity``: the
+    gfx950 sweep kernels have no conductivity form (RuntimeError); CPU tensors
+    run the K-single-steps definition with it."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -160,10 +180,11 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
     args = (src.dt, src.data_ptr(), dst.data_ptr(), list(src.n), src.gx, list(box), list(ux), list(D), sptr, slot,
             kernel)
     qptr = _source_ptr(src, source)
+    cptr = _cond_ptr(src, conductivity)
     if src.device.type == "cuda":
-        native().hip.stencil_sweep(*args, _stream_ptr(src.flat), qptr)
+        native().hip.stencil_sweep(*args, _stream_ptr(src.flat), qptr, cptr)
     else:
-        native().cpu.stencil_sweep(*args, qptr)
+        native().cpu.stencil_sweep(*args, qptr, cptr)
 
 
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
@@ -208,9 +229,12 @@ def unpack_box(f: PaddedField, box: Sequence[int], buf: torch.Tensor) -> None:
     native().hip.unpack_box(f.dt, f.data_ptr(), list(f.n), list(box), buf.data_ptr(), _stream_ptr(f.flat))
 
 
-def ftcs_reference(T: torch.Tensor, D: Sequence[float],
-                   src: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, float]:
+def ftcs_reference(T: torch.Tensor, D: Sequence[float], src: Optional[torch.Tensor] = None,
+                   cond: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, float]:
     """Plain-PyTorch FTCS on a ghosted block; returns (new interior, max |dT|).
+
+    ``cond``: optional ghosted block (shape of ``T``) of Ch = dtype(0.5 * c),
+    c the relative conductivity: the update of kernels.hpp ftcs_update_var.
 
     ``src``: optional heat source S = dtype(dt * q) on the interior points
     (shape of the result), added with one rounded addition after the update
@@ -218,11 +242,19 @@ def ftcs_reference(T: torch.Tensor, D: Sequence[float],
 
     Same arithmetic as the native backends (exactly rounded FMAs emulated with
     error-free transformations, utils/fma.py), so results compare bitwise."""
-    from ..utils.fma import ftcs_update
+    from ..utils.fma import ftcs_update, ftcs_update_var
+
+    def seven(F):
+        return (F[1:-1, 1:-1, 1:-1], F[:-2, 1:-1, 1:-1], F[2:, 1:-1, 1:-1], F[1:-1, :-2, 1:-1], F[1:-1, 2:, 1:-1],
+                F[1:-1, 1:-1, :-2], F[1:-1, 1:-1, 2:])
 
     c = T[1:-1, 1:-1, 1:-1]
-    new = ftcs_update(c, T[:-2, 1:-1, 1:-1], T[2:, 1:-1, 1:-1], T[1:-1, :-2, 1:-1], T[1:-1, 2:, 1:-1],
-                      T[1:-1, 1:-1, :-2], T[1:-1, 1:-1, 2:], D)
+    if cond is not None:
+        if cond.shape != T.shape or cond.dtype != T.dtype:
+            raise ValueError("cond must be a ghosted block of the shape and dtype of T")
+        new = ftcs_update_var(*seven(T), *seven(cond), D)
+    else:
+        new = ftcs_update(*seven(T), D)
     if src is not None:
         new = new + src.to(new.dtype)
     # residual in the field's precision (kernels.hpp resid_abs), widened for the max

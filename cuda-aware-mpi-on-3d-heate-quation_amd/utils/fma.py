@@ -86,3 +86,21 @@ def ftcs_update(c, xm, xp, ym, yp, zm, zp, D):
     ay = fma(-2.0, c, yp) + ym
     az = fma(-2.0, c, zp) + zm
     return fma(D[2], az, fma(D[1], ay, fma(D[0], ax, c)))
+
+
+def face_weight(h_here, h_there):
+    """Weight of the face between two vertices, the arithmetic mean of the
+    relative conductivity c: one rounded add of the stored Ch = dtype(0.5 c).
+    The add commutes, so both cells of a face get the same bits."""
+    return h_here + h_there
+
+
+def ftcs_update_var(c, xm, xp, ym, yp, zm, zp, hc, hxm, hxp, hym, hyp, hzm, hzp, D):
+    """FTCS update with a spatially varying conductivity in the native
+    backends' arithmetic (kernels.hpp ftcs_update_var): per axis the flux
+    f = fma(w+, T+ - T, w- * (T- - T)), then the same fused chain as
+    ``ftcs_update``."""
+    fx = fma(face_weight(hc, hxp), xp - c, face_weight(hc, hxm) * (xm - c))
+    fy = fma(face_weight(hc, hyp), yp - c, face_weight(hc, hym) * (ym - c))
+    fz = fma(face_weight(hc, hzp), zp - c, face_weight(hc, hzm) * (zm - c))
+    return fma(D[2], fz, fma(D[1], fy, fma(D[0], fx, c)))
