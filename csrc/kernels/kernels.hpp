@@ -34,6 +34,7 @@ struct KernelSpec {
   int O = -1; // TBL: output-store cache-policy bits (2 = nt)
   int NT = 0; // TBL: T^n ring size
   int ZS = 0; // TBL: tile stride along z (stored columns per tile; 0 = chosen per box)
+  int EW = 0; // TBL: edge role of a tile's two halo waves (0 = off, else 1 + the rows each also owns)
   bool multi_step() const { return kind == TBL; }
   static KernelSpec parse(const std::string& s);
   std::string str() const;

@@ -15,8 +15,11 @@ namespace hip {
 // every variant dispatch_tbl can launch, instantiated elsewhere
 #define H3D_V(T, R, WY, K, Q, N, S, P) \
   extern template void launch_tbl<T, R, WY, K, Q, N, S>(const StencilParams&, const KernelSpec&, hipStream_t);
+#define H3D_VE(T, R, WY, K, Q, N, S, EW, P) \
+  extern template void launch_tbl<T, R, WY, K, Q, N, S, false, EW>(const StencilParams&, const KernelSpec&, hipStream_t);
 #include "stencil_tbl_variants.inc"
 #undef H3D_V
+#undef H3D_VE
 #define H3D_VS(T, R, WY, K, Q, N, S, P) \
   extern template void launch_tbl<T, R, WY, K, Q, N, S, true>(const StencilParams&, const KernelSpec&, hipStream_t);
 #include "stencil_tbl_src_variants.inc"
@@ -92,7 +95,7 @@ static bool dispatch_tbl_src(const StencilParams* p, const KernelSpec& k, hipStr
       return true;
     }
   }
-  if (r.V != 1 || r.WZ != 1 || Q != 3) return false;
+  if (r.V != 1 || r.WZ != 1 || Q != 3 || r.EW != 0) return false;  // (the edge role has no source form)
   const int O = r.O > 0 ? r.O : 0;
 #define H3D_TBLS(RR, YY, KK, AA)                                      \
   if (R == RR && WY == YY && K == KK && O == (AA)) {                  \
@@ -147,12 +150,27 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
     }
   }
   if (r.V == 2) {  // two columns per lane: packed fp32 / 16-byte fp64 pairs (stencil_tbp.hip)
+    if (r.EW != 0) return false;  // (no edge role there)
     const DType t = sizeof(Real) == 8 ? DType::F64 : DType::F32;
     if (!p) return lean_pair_supported(t, k);
     stencil_lean_pair(t, *p, k, s);
     return true;
   }
   if (r.V != 1 || r.WZ != 1) return false;  // one value per lane, one wave across z
+  // Edge role (spec field 9 = 1 + E): the two halo waves of a tile evaluate only
+  // the stages inside its cone and own E more rows each.  fp64 K = 4, 12 waves of
+  // 4 rows, last residual only: 48-row tiles storing 40 rows (E = 0) and 52-row
+  // tiles storing 44 (E = 2)
+  if (r.EW != 0) {
+    if constexpr (sizeof(Real) == 8) {
+      if (R == 4 && WY == 12 && K == 4 && Q == 3 && r.O == (2 | kResidualLastOnly) && (r.EW == 1 || r.EW == 3)) {
+        if (p && r.EW == 1) launch_tbl<Real, 4, 12, 4, 3, 2 | kResidualLastOnly, false, false, 1>(*p, k, s);
+        if (p && r.EW == 3) launch_tbl<Real, 4, 12, 4, 3, 2 | kResidualLastOnly, false, false, 3>(*p, k, s);
+        return true;
+      }
+    }
+    return false;
+  }
 #define H3D_TBL(RR, YY, KK, QQ)                                    \
   if (R == RR && WY == YY && K == KK && Q == QQ && r.O <= 0) {     \
     if (p) launch_tbl<Real, RR, YY, KK, QQ>(*p, k, s);             \

@@ -30,6 +30,21 @@
 //     a Dirichlet face and waves on the tile's edge run the masked step (the
 //     same code with uniform x / y conditions and a per-lane z mask); the
 //     choice is a uniform branch per step, both forms hold one barrier;
+//   * a third form, the edge role (template parameter EW > 0, spec field 9):
+//     waves 0 and WY - 1 hold the tile's K halo rows, of which stage s is
+//     valid on tile rows [s + 1, TY - s - 1) only, so halo row j needs j of
+//     the K stages (6 of a 4 x 4 wave's 16 row-stages at K = 4).  Under the
+//     role those waves run a loop of their own whose step evaluates, per row,
+//     the stages inside that cone and nothing else, by static indices, so the
+//     stage rings outside the cone are never allocated; the registers and
+//     issue slots that frees carry E = EW - 1 owned rows per edge wave
+//     (TY = WY*R + 2E rows, TY - 2K stored: 52 / 44 at E = 2 against 48 / 40).
+//     The step is mask-free where every row of the wave is inside the box and
+//     the update range; on Dirichlet faces and in fill / drain it is the
+//     masked step restricted to the same cone.  An edge wave publishes the
+//     one LDS row its neighbour reads and holds the same barrier.  The three
+//     roles branch once per wave, never per step, which keeps each loop's
+//     live registers its own;
 //   * loads are an SGPR row base plus one lane offset (global_load saddr
 //     form), clamped rows / planes fold into the SGPR base.
 //
@@ -141,17 +156,19 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 #undef H3D_TBL_NAME
 #undef H3D_TBL_SRC
 
-template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false>
+// EW: the edge role of waves 0 and WY - 1 (0 = off, else 1 + their owned rows)
+template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false, int EW = 0>
 void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
   constexpr bool swap_xy = SW;
   // (if constexpr: only the form that is launched gets instantiated)
   const void* kfn = [] {
     if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
-    else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW>);
+    else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>);
   }();
+  static_assert(EW == 0 || !SRC, "the edge role has no source form");
   HEAT3D_CHECK(SRC == (p.src != nullptr), "tl: source form mismatch");
   Box b = p.box;
-  constexpr int TY = WY * R;
+  constexpr int TY = WY * R + 2 * (EW > 0 ? EW - 1 : 0);  // as the kernel's
   // swap_xy: march along y with x as the tile rows (thin x slabs: a tile of
   // WY*R x-rows covers the slab and its K-deep halos, workgroups march the
   // long y extent).  The kernel is axis-agnostic through its strides and
@@ -167,7 +184,7 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
     std::swap(b.hi[0], b.hi[1]);
   }
   HEAT3D_CHECK(Ln0 + 2 * Lg0 < (1LL << 30) && Ln1 + 2 * Lg1 < (1LL << 30) &&
-                   Lsy * (int64_t)sizeof(Real) * (R + 2 * Lg1 + TY + 2 * K) < (1LL << 31),
+                   Lsy * (int64_t)sizeof(Real) * (R + EW + 2 * Lg1 + TY + 2 * K) < (1LL << 31),
                "tl: extents exceed 32-bit tile coordinates");
   TBLArgs g{};
   g.sx = Lsx;
@@ -249,7 +266,7 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
                          static_cast<const Real*>(p.in), static_cast<Real*>(p.out), static_cast<const Real*>(p.src),
                          ga, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
     else
-    hipLaunchKernelGGL((stencil_tbl<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
+    hipLaunchKernelGGL((stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
                        s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, (Real)p.D[0], (Real)p.D[1],
                        (Real)p.D[2], r, done);
     HIPK_CHECK(hipGetLastError());

@@ -3,7 +3,12 @@
 // H3D_TBL_SRC 0, and stencil_tbl_src with H3D_TBL_SRC 1 (heat source, see the
 // comment there).  Textual inclusion keeps the kernel without a source exactly
 // the code it was before the source form existed.
-template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false>
+//
+// EW > 0: the edge role (impl.hpp, third step form).  Waves 0 and WY - 1 hold
+// the tile's K halo rows and E = EW - 1 owned rows next to them (R + E rows; the
+// tile has WY * R + 2E rows) and evaluate, for each row, only the stages whose
+// output lies inside the tile's cone.  EW = 0 is the kernel without the role.
+template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, int EW = 0>
 __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__ in, Real* __restrict__ out,
 #if H3D_TBL_SRC
                                                        const Real* __restrict__ src,
@@ -15,7 +20,11 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   // ((K-1)/K of a step of latency cover); Q >= 4 loads plane x+Q-2 at the
   // start of step x (Q-3 steps of cover)
   static_assert(Q == 3 || Q == 4 || Q == 6, "T^n ring size");
-  constexpr int TY = WY * R;
+  constexpr bool EDGE = EW > 0;
+  constexpr int E = EDGE ? EW - 1 : 0;  // owned rows of an edge wave
+  constexpr int RB = R + E;             // rows of an edge wave (register rows of every wave)
+  static_assert(!EDGE || (R >= K && WY >= 3 && !SW && !H3D_TBL_SRC), "edge role: halo-only waves, no source form");
+  constexpr int TY = WY * R + 2 * E;
   constexpr int YS = TY - 2 * K;   // tile stride along y (stored rows)
   // x-loop unroll making every ring index and the LDS parity static
   constexpr int U = lcm_l(lcm_l(Q, 3), 2);
@@ -81,7 +90,9 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   const int lane = threadIdx.x & 63;
   const int c0 = g.c00 + zb * zs;         // tile's first loaded column
   const int r0 = g.r00 + ybk * YS;          // tile's first loaded row
-  const int yb = r0 + wave * R;             // this wave's first row
+  // first tile row of this wave (edge role: wave 0 holds R + E rows)
+  const int tr0 = EDGE && wave > 0 ? E + wave * R : wave * R;
+  const int yb = r0 + tr0;                  // this wave's first row
   const int col = c0 + lane;
   const int xa = g.blo[0] + xlo_p, xe = g.blo[0] + xhi_p;
   const int x0 = xa - (K - 1), xlast = xe + K - 2;
@@ -89,7 +100,7 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
 
   // ---- uniform (per wave) classification
   const bool zfast = c0 >= g.uzlo && c0 + 64 <= g.uzhi;
-  const bool wrows = wave * R >= K && wave * R + R <= TY - K && yb >= g.uylo && yb + R <= g.uyhi &&
+  const bool wrows = tr0 >= K && tr0 + R <= TY - K && yb >= g.uylo && yb + R <= g.uyhi &&
                      yb >= g.blo[1] && yb + R <= g.bhi[1];
   const bool wfast = zfast && wrows;
   // steps whose every stage is valid, updated, counted and (last stage) stored
@@ -99,19 +110,20 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   // masked form, per row r (uniform, one SGPR): bit r = row in the update
   // range, bit R + r = stored row, bit 2R + s*R + r = row counted at stage s
   // (64-bit when the rows x stages outgrow one SGPR: 8-wave tiles of 6 rows)
-  using YMask = std::conditional_t<(2 * R + K * R <= 32), unsigned, unsigned long long>;
-  static_assert(2 * R + K * R <= 64, "row mask bits");
+  // (edge role: RB rows per field, as an edge wave holds)
+  using YMask = std::conditional_t<(2 * RB + K * RB <= 32), unsigned, unsigned long long>;
+  static_assert(2 * RB + K * RB <= 64, "row mask bits");
   YMask ybits = 0;
 #pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const int row = yb + r, rp = wave * R + r;
+  for (int r = 0; r < RB; ++r) {
+    const int row = yb + r, rp = tr0 + r;
     if (row >= g.uylo && row < g.uyhi) ybits |= YMask(1) << r;
-    if (rp >= K && rp < TY - K && row >= g.blo[1] && row < g.bhi[1]) ybits |= YMask(1) << (R + r);
+    if (rp >= K && rp < TY - K && row >= g.blo[1] && row < g.bhi[1]) ybits |= YMask(1) << (RB + r);
 #pragma unroll
     for (int s = 0; s < K; ++s)
       if (row >= g.uylo && row < g.uyhi && rp >= s + 1 && rp < TY - s - 1 && row >= g.blo[1] - (K - 1 - s) &&
           row < g.bhi[1] + (K - 1 - s))
-        ybits |= YMask(1) << (2 * R + s * R + r);
+        ybits |= YMask(1) << (2 * RB + s * RB + r);
   }
   if constexpr (sizeof(YMask) == 4) {
     ybits = (unsigned)sgpr((int)ybits);
@@ -138,63 +150,88 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   const Real* __restrict__ srcw = src + (g.origin + (int64_t)ybc * g.sy + c0);
 #endif
   // row byte offsets (clamped rows fold in), 0 <= roff < 2^31: checked in launch_tbl
-  int roff[R];
+  int roff[RB];
 #pragma unroll
-  for (int r = 0; r < R; ++r) roff[r] = sgpr((yclamp(yb + r) - ybc) * (int)g.sy * (int)sizeof(Real));
+  for (int r = 0; r < RB; ++r) roff[r] = sgpr((yclamp(yb + r) - ybc) * (int)g.sy * (int)sizeof(Real));
   const int sy_b = (int)g.sy * (int)sizeof(Real);
   const unsigned lane_b = (unsigned)lane * (unsigned)sizeof(Real);
 
-  Real q[Q][R];              // T^n ring: plane p in slot (p - x0 + 1) mod Q
-  Real f[K - 1][3][R];       // F_{s+1}(p) in f[s][(p + s) mod 3]
+  Real q[Q][RB];             // T^n ring: plane p in slot (p - x0 + 1) mod Q
+  Real f[K - 1][3][RB];      // F_{s+1}(p) in f[s][(p + s) mod 3]
   Real m[K];                 // per-lane residual maxima (field precision, widened at the end)
   bool nan_seen = false;
 #pragma unroll
   for (int s = 0; s < K; ++s) m[s] = Real(0);
+  if constexpr (!EDGE) {
 #pragma unroll
-  for (int s = 0; s < K - 1; ++s)
+    for (int s = 0; s < K - 1; ++s)
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
+      for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int r = 0; r < R; ++r) f[s][i][r] = Real(0);
+        for (int r = 0; r < R; ++r) f[s][i][r] = Real(0);
+  }
 
-  auto load_plane = [&](int x, Real (&d)[R]) {
+  // rows [B, N) of plane x
+  auto load_rows = [&](int x, Real (&d)[RB], auto b_tag, auto n_tag) {
+    const int xc = min(max(x, g.xlo_live), g.xhi_live);
+    const __amdgpu_buffer_rsrc_t rs = plane_rsrc(inw + (int64_t)xc * sx);
+#pragma unroll
+    for (int r = decltype(b_tag)::value; r < decltype(n_tag)::value; ++r) d[r] = buf_load<Real>(rs, lane_b, roff[r]);
+  };
+  auto load_plane = [&](int x, Real (&d)[RB]) {
     const int xc = min(max(x, g.xlo_live), g.xhi_live);
     const __amdgpu_buffer_rsrc_t rs = plane_rsrc(inw + (int64_t)xc * sx);
 #pragma unroll
     for (int r = 0; r < R; ++r) d[r] = buf_load<Real>(rs, lane_b, roff[r]);
   };
   constexpr int NPRE = Q == 3 ? 3 : Q - 1;  // planes resident / in flight before step x0
+  if constexpr (!EDGE) {
 #pragma unroll
-  for (int i = 0; i < NPRE; ++i) load_plane(x0 - 1 + i, q[i]);
+    for (int i = 0; i < NPRE; ++i) load_plane(x0 - 1 + i, q[i]);
+  }
 
-  // One plane step.  FAST: every condition below is known true.
-  auto step = [&](auto fast_tag, const int x, auto ph_tag) {
+  // One plane step.  FAST: every condition below is known true.  ROLE: 0 an
+  // interior wave (R rows, every stage); 1 / 2 the edge role of wave 0 /
+  // WY - 1: RB rows, and of row r only the stages inside the tile's cone
+  // (static, so the stage rings outside it are never allocated).  The stage-s
+  // output of tile row rp is read only by stage s + 1 of rows rp - 1 .. rp + 1,
+  // and stage s is valid on rows [s + 1, TY - s - 1): everything a cone value
+  // reads is in the cone, whatever the masks say.
+  auto step = [&](auto fast_tag, const int x, auto ph_tag, auto role_tag) {
     constexpr bool FAST = decltype(fast_tag)::value;
     constexpr int ph = decltype(ph_tag)::value;
+    constexpr int ROLE = decltype(role_tag)::value;
+    constexpr int NR = ROLE ? RB : R;
+    // is stage s of local row r inside the cone?
+    auto live = [](int r, int s) constexpr { return ROLE == 0 || (ROLE == 1 ? s < r : s < RB - 1 - r); };
     constexpr int sM = ph % Q, sC = (ph + 1) % Q, sP = (ph + 2) % Q;
     constexpr int fw = ph % 3, fc = (ph + 2) % 3, fm = (ph + 1) % 3;
     constexpr int par = ph & 1;  // LDS buffer (U is even)
-    if constexpr (Q >= 4) load_plane(x + Q - 2, q[(ph + Q - 1) % Q]);
+    if constexpr (Q >= 4) {
+      if constexpr (!EDGE) load_plane(x + Q - 2, q[(ph + Q - 1) % Q]);
+      else load_rows(x + Q - 2, q[(ph + Q - 1) % Q], std::integral_constant<int, 0>{}, std::integral_constant<int, NR>{});
+    }
     // publish the edge rows of every stage's centre plane
 #pragma unroll
     for (int s = 0; s < K; ++s) {
-      const Real(&C)[R] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
-      s_row[par][s][wave][0][lane] = C[0];
-      s_row[par][s][wave][1][lane] = C[R - 1];
+      const Real(&C)[RB] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
+      // (an edge wave publishes the row its one neighbour reads)
+      if constexpr (ROLE != 1) s_row[par][s][wave][0][lane] = C[0];
+      if constexpr (ROLE != 2) s_row[par][s][wave][1][lane] = C[NR - 1];
     }
     __syncthreads();
     const int wl = max(wave - 1, 0), wh = min(wave + 1, WY - 1);
 #pragma unroll
     for (int s = 0; s < K; ++s) {
-      Real(&M)[R] = s == 0 ? q[sM] : f[s > 0 ? s - 1 : 0][fm];
-      Real(&C)[R] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
-      Real(&P)[R] = s == 0 ? q[sP] : f[s > 0 ? s - 1 : 0][fw];
+      Real(&M)[RB] = s == 0 ? q[sM] : f[s > 0 ? s - 1 : 0][fm];
+      Real(&C)[RB] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
+      Real(&P)[RB] = s == 0 ? q[sP] : f[s > 0 ? s - 1 : 0][fw];
       const Real lo = s_row[par][s][wl][1][lane];
       const Real hi = s_row[par][s][wh][0][lane];
       const int p = x - s;
 #if H3D_TBL_SRC
       // the source rows of this stage's plane (clamped as load_plane)
-      Real S[R];
+      Real S[RB];
       {
         const int pc = min(max(p, g.xlo_live), g.xhi_live);
         const __amdgpu_buffer_rsrc_t rs = plane_rsrc(srcw + (int64_t)pc * sx);
@@ -210,9 +247,10 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         xst = p >= xa && p < xe;
       }
 #pragma unroll
-      for (int r = 0; r < R; ++r) {
+      for (int r = 0; r < NR; ++r) {
+        if (!live(r, s)) continue;
         const Real ym = r == 0 ? lo : C[r > 0 ? r - 1 : 0];
-        const Real yp = r == R - 1 ? hi : C[r + 1 < R ? r + 1 : 0];
+        const Real yp = r == NR - 1 ? hi : C[r + 1 < NR ? r + 1 : 0];
         const Real zm = dpp_shr1z(C[r]);
         const Real zp = dpp_shl1z(C[r]);
         // same operation order as kernels.hpp ftcs_update in both frames
@@ -228,11 +266,11 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         bool upd = true, cnt = true, st = true;
         if constexpr (!FAST) {
           upd = xin && ((ybits >> r) & 1);
-          cnt = xcnt && ((ybits >> (2 * R + s * R + r)) & 1);
-          st = xst && ((ybits >> (R + r)) & 1);
+          cnt = xcnt && ((ybits >> (2 * RB + s * RB + r)) & 1);
+          st = xst && ((ybits >> (RB + r)) & 1);
         }
         if (s < K - 1) {
-          Real(&N)[R] = f[s < K - 1 ? s : 0][fw];
+          Real(&N)[RB] = f[s < K - 1 ? s : 0][fw];
           if constexpr (FAST) N[r] = nv;
           else N[r] = (upd && zin) ? nv : C[r];
         }
@@ -250,20 +288,59 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         }
       }
       if constexpr (Q == 3) {
-        if (s == 0) load_plane(x + 2, q[sM]);  // the slot stage 0 has just freed
+        // the slot stage 0 has just freed
+        if constexpr (!EDGE) {
+          if (s == 0) load_plane(x + 2, q[sM]);
+        } else {
+          if (s == 0) load_rows(x + 2, q[sM], std::integral_constant<int, 0>{}, std::integral_constant<int, NR>{});
+        }
       }
     }
   };
 
   // whole chunks of U steps (the unrolled body needs a constant trip count);
   // padded steps past xlast take the masked form and count / store nothing
-  for (int xb = x0; xb <= xlast; xb += U) {
-    static_for<0, U>([&](auto ph_tag) {
-      constexpr int ph = decltype(ph_tag)::value;
-      const int x = xb + ph;
-      if (wfast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag);
-      else step(std::false_type{}, x, ph_tag);
-    });
+  auto run = [&](auto role_tag, const bool fast) {
+    if constexpr (EDGE) {
+      // the rings are set up per role: nothing of one role's loop is live in another's
+      constexpr int NR = decltype(role_tag)::value ? RB : R;
+#pragma unroll
+      for (int s = 0; s < K - 1; ++s)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int r = 0; r < NR; ++r) f[s][i][r] = Real(0);
+#pragma unroll
+      for (int i = 0; i < NPRE; ++i)
+        load_rows(x0 - 1 + i, q[i], std::integral_constant<int, 0>{}, std::integral_constant<int, NR>{});
+    }
+    for (int xb = x0; xb <= xlast; xb += U) {
+      static_for<0, U>([&](auto ph_tag) {
+        constexpr int ph = decltype(ph_tag)::value;
+        const int x = xb + ph;
+        if (fast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag, role_tag);
+        else step(std::false_type{}, x, ph_tag, role_tag);
+      });
+    }
+  };
+  if constexpr (EDGE) {
+    // Edge waves: a loop of their own (a role per wave, never per step, keeps
+    // the register rows of the other role dead in each loop).  Mask-free
+    // where every row is inside the box and the update range: then every
+    // cone value is updated, counted and (owned rows, last stage) stored.
+    const bool efast = zfast && yb >= max(g.uylo, g.blo[1]) && yb + RB <= min(g.uyhi, g.bhi[1]);
+    if (wave == 0) run(std::integral_constant<int, 1>{}, efast);
+    else if (wave == WY - 1) run(std::integral_constant<int, 2>{}, efast);
+    else run(std::integral_constant<int, 0>{}, wfast);
+  } else {
+    for (int xb = x0; xb <= xlast; xb += U) {
+      static_for<0, U>([&](auto ph_tag) {
+        constexpr int ph = decltype(ph_tag)::value;
+        const int x = xb + ph;
+        if (wfast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag, std::integral_constant<int, 0>{});
+        else step(std::false_type{}, x, ph_tag, std::integral_constant<int, 0>{});
+      });
+    }
   }
 
   // this piece's residuals (the lane masks depend on its tile)

@@ -78,12 +78,14 @@ KernelSpec KernelSpec::parse(const std::string& s) {
     k.NT = at(6);
     if (k.kind != Tile && parts.size() > 7) k.O = at(7);  // store cache-policy bits
     if (k.kind != Tile && parts.size() > 8) k.ZS = at(8);  // z tile stride
+    if (k.kind != Tile && parts.size() > 9) k.EW = at(9);  // edge role (1 + owned rows of the halo waves)
+    if (k.EW < 0) throw UsageError("kernel '" + s + "': the edge-role field is 0 (off) or 1 + rows");
   } else if (h == "column" || h == "tb2" || h == "tbk2" || (h.size() == 3 && h[0] == 't' && (h[1] == 'b' || h[1] == 'r'))) {
     throw UsageError("kernel '" + s + "' was retired in round 3 (the column / queue / register-ring kernels); "
                      "use tile for single steps and tl2..tl6 for K-step sweeps");
   } else {
     throw UsageError("unknown kernel '" + s + "' (auto | naive | tile[:V[:R[:WZ[:WY]]]] | "
-                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS]]]]]]]])");
+                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS[:EDGE]]]]]]]]])");
   }
   return k;
 }
@@ -172,8 +174,9 @@ std::string KernelSpec::str() const {
   std::ostringstream os;
   os << (kind == Tile ? std::string("tile:") : "tl" + std::to_string(K) + ":") << V << ":" << R << ":" << WZ << ":"
      << WY << ":" << L << ":" << NT;
-  if (kind != Tile && (O > 0 || ZS > 0)) os << ":" << O;
-  if (kind != Tile && ZS > 0) os << ":" << ZS;
+  if (kind != Tile && (O > 0 || ZS > 0 || EW > 0)) os << ":" << O;
+  if (kind != Tile && (ZS > 0 || EW > 0)) os << ":" << ZS;
+  if (kind != Tile && EW > 0) os << ":" << EW;
   return os.str();
 }
 
@@ -230,6 +233,14 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
   // form, stencil_tbp.hip); --kernel2 tlK:... / tsK:... picks a variant
   if (!kspec2_.multi_step()) kspec2_.kind = KernelSpec::TBL;
   kspec2_.K = K;
+  if (kspec2_.EW > 0) {
+    edge_last_ = kspec2_;
+    edge_last_.O = (edge_last_.O > 0 ? edge_last_.O : 0) | kResidualLastOnly;
+    edge_last_set_ = true;
+    kspec2_ = KernelSpec{};
+    kspec2_.kind = KernelSpec::TBL;
+    kspec2_.K = K;
+  }
   int64_t min_n[3] = {INT64_MAX, INT64_MAX, INT64_MAX};
   for (const auto& sd : dec_.subs)
     for (int a = 0; a < 3; ++a) min_n[a] = std::min(min_n[a], sd.n[a]);
@@ -1029,6 +1040,14 @@ void Solver::calibrate_remainders() {
     const KernelSpec t = KernelSpec::parse("tl4:1:4:1:12:0:3:66");
     if (hip::lean_supported(dt_, t, has_source_))
       cands.push_back({K_ + 1, t, "sweep" + std::to_string(K_ + 1) + "[" + t.str() + "]", spec_for_depth(K_ + 1)});
+    // ... and the same 12 waves with the edge role (spec field 9): the two
+    // halo waves evaluate only the stages inside the tile's cone, and with two
+    // owned rows each the tile stores 44 of 52 rows
+    for (const char* v : {"tl4:1:4:1:12:0:3:66:0:1", "tl4:1:4:1:12:0:3:66:0:3"}) {
+      const KernelSpec e = KernelSpec::parse(v);
+      if (hip::lean_supported(dt_, e, has_source_))
+        cands.push_back({K_ + 1, e, "sweep" + std::to_string(K_ + 1) + "[" + e.str() + "]", spec_for_depth(K_ + 1)});
+    }
   }
   const bool pick_form = pick_sweep_form();
   if (pick_form) {
@@ -1558,6 +1577,7 @@ bool Solver::residual_last_ok() const {
 }
 
 KernelSpec Solver::last_only(const KernelSpec& ks) const {
+  if (edge_last_set_ && ks.K == edge_last_.K && ks.V == 0 && ks.R == 0 && ks.WY == 0 && ks.NT == 0) return edge_last_;
   KernelSpec r = ks.resolved(dt_);
   r.O = (r.O > 0 ? r.O : 0) | kResidualLastOnly;
   return r;

@@ -356,6 +356,11 @@ class Solver {
   bool rl_d_[8] = {};
   bool long_major_ = false;          // K+1 sweeps cheaper per step (calibrate_remainders, long_sweeps_for)
   KernelSpec ks_last_[8];
+  // --kernel2 with the edge role (spec field 9): those shapes exist as
+  // last-residual forms only, so the sweeps that need every residual run the
+  // depth's default shape (kspec2_) and last_only() of it is this shape
+  KernelSpec edge_last_;
+  bool edge_last_set_ = false;
   KernelSpec rl_pick_[8];            // per depth: the variant the start-up timing kept
   // lagged overlapped sweeps: the all-reduce of sweep q is issued after the
   // halo of sweep q+1 (see enqueue_multi); flush issues a pending one
