@@ -190,26 +190,31 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   H3D_TBLA(3, 12, 4, 2 | kResidualLastOnly)
   if constexpr (sizeof(Real) == 8) {
     // fp64 48-row K = 4 and 36-row K = 5 tiles of 12 waves: 167 VGPRs without
-    // the K - 1 residual maxima
+    // the K - 1 residual maxima.  (With every residual these shapes spill, and
+    // launch_tbl refuses a spilling variant: they exist in this form only.)
     H3D_TBLA(4, 12, 4, 2 | kResidualLastOnly) H3D_TBLA(3, 12, 5, 2 | kResidualLastOnly)
   }
   H3D_TBLA(2, 16, 4, 2) H3D_TBLA(3, 16, 2, 2) H3D_TBLA(5, 16, 2, 2)
   H3D_TBLA(3, 12, 4, 2)  // the fp64 K = 4 default (long sweeps: 12 waves, 36 rows)
-  H3D_TBLA(4, 12, 4, 2)
+  if constexpr (sizeof(Real) == 4) {
+    H3D_TBLA(4, 12, 4, 2)
+  }
 #undef H3D_TBLA
   // 16 waves (<= 128 VGPRs, LDS 2K x 16 KiB): K <= 4; 12 waves (<= 168 VGPRs): K = 5
-  H3D_TBL(3, 16, 4, 3) H3D_TBL(3, 16, 4, 4) H3D_TBL(3, 16, 3, 3) H3D_TBL(3, 16, 3, 4)
-  H3D_TBL(2, 16, 4, 3) H3D_TBL(2, 16, 4, 4) H3D_TBL(2, 16, 5, 3) H3D_TBL(2, 16, 3, 3)
+  H3D_TBL(3, 16, 3, 3) H3D_TBL(3, 16, 3, 4)
+  H3D_TBL(2, 16, 4, 3) H3D_TBL(2, 16, 4, 4) H3D_TBL(2, 16, 3, 3)
   H3D_TBL(2, 16, 4, 6) H3D_TBL(2, 16, 3, 6) H3D_TBL(3, 16, 3, 6) H3D_TBL(2, 16, 2, 6)
   H3D_TBL(3, 16, 2, 3) H3D_TBL(2, 16, 2, 3)
-  H3D_TBL(4, 12, 4, 3) H3D_TBL(4, 12, 4, 4) H3D_TBL(4, 12, 5, 3) H3D_TBL(3, 12, 5, 3) H3D_TBL(3, 12, 4, 3)
+  H3D_TBL(3, 12, 4, 3)
   // 8 waves (<= 256 VGPRs, 2 per SIMD): 48-row tiles at K = 4; the fp64 K = 5 / 6 defaults
   H3D_TBL(6, 8, 4, 3) H3D_TBL(6, 8, 3, 3) H3D_TBL(6, 8, 4, 4) H3D_TBL(5, 8, 4, 3)
   H3D_TBL(3, 8, 5, 3) H3D_TBL(3, 8, 6, 3)
   if constexpr (sizeof(Real) == 4) {
     // fp32: half the registers and LDS per row, so deeper sweeps fit 16 waves
-    H3D_TBL(4, 16, 4, 3) H3D_TBL(3, 16, 5, 3) H3D_TBL(4, 16, 5, 3) H3D_TBL(3, 16, 6, 3)
-    H3D_TBL(4, 16, 6, 3) H3D_TBL(4, 16, 4, 4) H3D_TBL(3, 16, 5, 6)
+    // and the taller tiles 12 (in fp64 each of these shapes spills: not built)
+    H3D_TBL(3, 16, 4, 3) H3D_TBL(3, 16, 4, 4) H3D_TBL(2, 16, 5, 3)
+    H3D_TBL(4, 12, 4, 3) H3D_TBL(4, 12, 4, 4) H3D_TBL(4, 12, 5, 3) H3D_TBL(3, 12, 5, 3)
+    H3D_TBL(4, 16, 4, 3) H3D_TBL(3, 16, 5, 3) H3D_TBL(4, 16, 4, 4) H3D_TBL(3, 16, 5, 6)
   }
 #undef H3D_TBL
   return false;

@@ -216,6 +216,13 @@ PYBIND11_MODULE(_heat3d, m) {
   m.def("kernel_spec_resolved", [](const std::string& spec, const std::string& dtype) {
     return heat3d::KernelSpec::parse(spec).resolved(dtype == "fp32" ? heat3d::DType::F32 : heat3d::DType::F64).str();
   });
+  // is the lean sweep variant the spec resolves to for dtype instantiated (with_source:
+  // its heat-source form)?  No device access (tests/test_lean_variants_cpu.py)
+  m.def("lean_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
+    const heat3d::KernelSpec k = heat3d::KernelSpec::parse(spec);
+    if (!k.multi_step()) throw UsageError("lean_supported needs a tl2..tl6 kernel");
+    return heat3d::hip::lean_supported(dt_of(dtype), k, with_source);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false);
   m.def("rccl_unique_id", []() { return py::bytes(rccl_unique_id()); });
   m.def("rccl_version", &rccl_version);
   // the HIP runtime / RCCL this process is bound to (bench JSON "runtime")
