@@ -107,6 +107,8 @@ std::string Config::usage() {
      << "                            float64, NX*NY*NZ values, z fastest (the checkpoint field file's order)\n"
      << "  --conductivity FILE       relative conductivity c, 0 < c <= 1 (T_t = div(alpha c grad T) + q), same format\n"
      << "                            as --source; iterations then run as single steps (no K-step sweeps)\n"
+     << "  --conductivity-sweeps     with a conductivity field: K-step sweeps of the tv kernels (tv2 / tv3,\n"
+     << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -253,6 +255,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--source") c.source_file = get("--source");
     else if (key == "--initial") c.initial_file = get("--initial");
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
+    else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
     else if (key == "--json-out") c.json_out = get("--json-out");
     else if (key == "--verbose") c.verbose = (int)to_i64(get("--verbose"), "--verbose");
     else if (key == "--progress") c.progress_s = to_f64(get("--progress"), "--progress");
@@ -371,6 +374,8 @@ Config Config::parse(int argc, const char* const* argv) {
     throw UsageError("--source / --initial / --conductivity are not part of --scheme reference");
   if (!c.conductivity_file.empty() && c.compat)
     throw UsageError("--conductivity is not part of --compat (the reference's uniform material)");
+  if (c.cond_sweeps && c.compat)
+    throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
   return c;
 }
 

@@ -66,6 +66,9 @@ struct Config {
   std::string checkpoint_dir;
   std::string restart;
   std::string source_file;   // --source: heat source q, raw float64 NX*NY*NZ
+  // --conductivity-sweeps: with a conductivity field, K-step sweeps of the tv
+  // kernel family (stencil_tbv.hip) instead of single steps.  Off by default.
+  bool cond_sweeps = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   std::string json_out;

@@ -25,7 +25,9 @@ struct KernelSpec {
   // stencil_tbp.hip), K time steps per HBM sweep.  The round-1/2 queue and
   // register-ring sweep kernels (tb2 / tbK / trK) were retired in round 3:
   // no default path used them (docs/PERFORMANCE.md keeps their numbers).
-  enum Kind { Naive = 0, Tile = 2, TBL = 6 } kind = Tile;
+  // TBV: the K-step sweep with a conductivity field (stencil_tbv.hip; spec
+  // tv2 / tv3), one shape per dtype and depth.
+  enum Kind { Naive = 0, Tile = 2, TBL = 6, TBV = 7 } kind = Tile;
   int K = 0;  // multi-step kinds: time steps per sweep
   int WZ = 0, WY = 0;  // waves per workgroup along z and y
   int V = 0;  // elements per lane along z (0 = default for dtype)
@@ -35,7 +37,7 @@ struct KernelSpec {
   int NT = 0; // TBL: T^n ring size
   int ZS = 0; // TBL: tile stride along z (stored columns per tile; 0 = chosen per box)
   int EW = 0; // TBL: edge role of a tile's two halo waves (0 = off, else 1 + the rows each also owns)
-  bool multi_step() const { return kind == TBL; }
+  bool multi_step() const { return kind == TBL || kind == TBV; }
   static KernelSpec parse(const std::string& s);
   std::string str() const;
   // zero (default) fields replaced by the tuned defaults for dtype t
@@ -81,8 +83,9 @@ struct StencilParams {
   // relative conductivity, stored as Ch = dtype(0.5 * c) with 0 < c <= 1: a
   // static field in the same Layout (ghost shells included; a face weight
   // towards a ghost point reads Ch there).  Every updated point is evaluated
-  // by ftcs_update_var.  nullptr: uniform material, the kernels above.  Only
-  // single-step kernels have a conductivity form (a sweep with it is an error).
+  // by ftcs_update_var.  nullptr: uniform material, the kernels above.  The
+  // single-step kernels and the tv sweeps have a conductivity form (a tl sweep
+  // with it is an error, as is a tv sweep without it).
   const void* cond = nullptr;
 };
 
@@ -150,6 +153,13 @@ int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, 
 // Is the lean kernel variant that k resolves to for dtype t instantiated?
 // with_source: its heat-source form (StencilParams::src != nullptr)
 bool lean_supported(DType t, const KernelSpec& k, bool with_source = false);
+// K-step sweep with a conductivity field (stencil_tbv.hip; spec tvK): needs
+// p.cond, honours p.src; no fused check, no schedule tuning
+void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
+// Is the tv kernel of k's depth built for dtype t (with_source: its heat-source form)?
+bool cond_sweep_supported(DType t, const KernelSpec& k, bool with_source);
+// deepest tv depth built for dtype t
+int cond_sweep_max_depth(DType t);
 // Any multi-step kind -> its kernel
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 void pack_box(DType t, const void* f, const Layout& L, const Box& b, void* buf, void* stream);

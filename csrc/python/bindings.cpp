@@ -223,6 +223,10 @@ PYBIND11_MODULE(_heat3d, m) {
     if (!k.multi_step()) throw UsageError("lean_supported needs a tl2..tl6 kernel");
     return heat3d::hip::lean_supported(dt_of(dtype), k, with_source);
   }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false);
+  // is the tv sweep (conductivity form) of the spec's depth built for dtype?  No device access
+  m.def("cond_sweep_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
+    return heat3d::hip::cond_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec), with_source);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false);
   m.def("rccl_unique_id", []() { return py::bytes(rccl_unique_id()); });
   m.def("rccl_version", &rccl_version);
   // the HIP runtime / RCCL this process is bound to (bench JSON "runtime")

@@ -80,12 +80,26 @@ KernelSpec KernelSpec::parse(const std::string& s) {
     if (k.kind != Tile && parts.size() > 8) k.ZS = at(8);  // z tile stride
     if (k.kind != Tile && parts.size() > 9) k.EW = at(9);  // edge role (1 + owned rows of the halo waves)
     if (k.EW < 0) throw UsageError("kernel '" + s + "': the edge-role field is 0 (off) or 1 + rows");
+  } else if (h.size() == 3 && h[0] == 't' && h[1] == 'v' && h[2] >= '2' && h[2] <= '4') {
+    // tv2..tv4 = K-step sweep with a conductivity field; one shape per depth,
+    // only the schedule fields (x segment length, z tile stride) are read
+    k.kind = TBV;
+    k.K = h[2] - '0';
+    auto at = [&](std::size_t i) { return parts.size() > i ? std::atoi(parts[i].c_str()) : 0; };
+    k.V = at(1);
+    k.R = at(2);
+    k.WZ = at(3);
+    k.WY = at(4);
+    k.L = at(5);
+    k.NT = at(6);
+    if (parts.size() > 7) k.O = at(7);
+    if (parts.size() > 8) k.ZS = at(8);
   } else if (h == "column" || h == "tb2" || h == "tbk2" || (h.size() == 3 && h[0] == 't' && (h[1] == 'b' || h[1] == 'r'))) {
     throw UsageError("kernel '" + s + "' was retired in round 3 (the column / queue / register-ring kernels); "
                      "use tile for single steps and tl2..tl6 for K-step sweeps");
   } else {
     throw UsageError("unknown kernel '" + s + "' (auto | naive | tile[:V[:R[:WZ[:WY]]]] | "
-                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS[:EDGE]]]]]]]]])");
+                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS[:EDGE]]]]]]]]] | tv2..tv3)");
   }
   return k;
 }
@@ -172,7 +186,7 @@ KernelSpec KernelSpec::resolved(DType t) const {
 std::string KernelSpec::str() const {
   if (kind == Naive) return "naive";
   std::ostringstream os;
-  os << (kind == Tile ? std::string("tile:") : "tl" + std::to_string(K) + ":") << V << ":" << R << ":" << WZ << ":"
+  os << (kind == Tile ? std::string("tile:") : (kind == TBV ? "tv" : "tl") + std::to_string(K) + ":") << V << ":" << R << ":" << WZ << ":"
      << WY << ":" << L << ":" << NT;
   if (kind != Tile && (O > 0 || ZS > 0 || EW > 0)) os << ":" << O;
   if (kind != Tile && (ZS > 0 || EW > 0)) os << ":" << ZS;
@@ -213,8 +227,15 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
                                << comm_->size() << " ranks");
   dec_ = Decomposition::make(cfg_.n, dims);
   kspec_ = KernelSpec::parse(cfg_.kernel);
-  if (kspec_.kind == KernelSpec::TBL) kspec_.kind = KernelSpec::Tile;
+  if (kspec_.multi_step()) kspec_.kind = KernelSpec::Tile;
   kspec2_ = KernelSpec::parse(cfg_.kernel2);
+  // (the tv family is chosen by --conductivity-sweeps, not by --kernel2: it only gives the depth)
+  if (kspec2_.kind == KernelSpec::TBV) {
+    const int k2 = kspec2_.K;
+    kspec2_ = KernelSpec{};
+    kspec2_.kind = KernelSpec::TBL;
+    kspec2_.K = k2;
+  }
   overlap_ = cfg_.overlap;
 
   // K-step temporal blocking: on by default on the GPU, opt-in on the CPU
@@ -250,6 +271,7 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
   for (int a = 0; a < 3; ++a) fits &= dims[a] == 1 || min_n[a] >= K;
   tb_ = kspec_.kind != KernelSpec::Naive && (cfg_.temporal >= 2 || (cfg_.temporal == 0 && be_->is_gpu())) && fits;
   K_ = tb_ ? K : 1;
+  Kc_ = !tb_ ? 0 : be_->is_gpu() ? std::min(K_, hip::cond_sweep_max_depth(dt_)) : K_;
   for (int a = 0; a < 3; ++a) hd_[a] = xd_[a] = tb_ && dims[a] > 1 ? K : 1;
   ordered_halo_ = tb_ && block;
   // overlapped sweeps need a non-empty interior between the boundary layers
@@ -635,7 +657,8 @@ void Solver::retune() {
   }
   rl_ = false;
   for (bool& b : rl_d_) b = false;
-  // a conductivity field: single steps only, nothing to time
+  // a conductivity field: single steps, or the tv sweeps (one shape per
+  // depth, every residual): nothing to time
   if (has_cond_) return;
   tune_schedules();
   calibrate_remainders();
@@ -737,7 +760,7 @@ void Solver::canary_stream_graphs() {
     sg_state_ = "unverified";
     return;
   }
-  const int64_t cyc = sweeping() ? (int64_t)K_ * (nbuf_ == 3 ? 6 : 2) : (nbuf_ == 3 ? 6 : 2);
+  const int64_t cyc = sweeping() ? (int64_t)sweep_depth() * (nbuf_ == 3 ? 6 : 2) : (nbuf_ == 3 ? 6 : 2);
   const int G = graph_len_for(cyc);
   if (G <= 0) {
     sg_state_ = "unverified";
@@ -914,6 +937,12 @@ void Solver::tune_schedules() {
 // the next buffer, no residual state, as tune_schedules) and the ranks agree
 // by vote: long for remainder r only where every rank found it cheaper.
 KernelSpec Solver::spec_for_depth(int Kp) const {
+  if (cond_sweeping()) {
+    KernelSpec kv;
+    kv.kind = KernelSpec::TBV;
+    kv.K = Kp;
+    return kv;
+  }
   if (Kp == K_) return kspec2_;
   if (Kp >= 0 && Kp < 8 && depth_set_[Kp]) return depth_spec_[Kp];
   KernelSpec ks;
@@ -1220,7 +1249,8 @@ int Solver::preheat(int sweeps) {
   // only rewritten while no rollback can need it, and then with the values
   // the next sweep writes there anyway (a sweep is idempotent).
   join_pipeline();
-  const int Kp = K_;
+  const int Kp = sweep_depth();
+  const KernelSpec kpre = cond_sweeping() ? spec_for_depth(Kp) : kspec2_;
   int n = 0;
   for (int i = 0; i < sweeps; ++i) {
     for (auto& l : local_) {
@@ -1243,7 +1273,7 @@ int Solver::preheat(int sweeps) {
       shrink(l.ux, l.sd.n[0], sp.ux);
       shrink(l.uy, l.sd.n[1], sp.uy);
       shrink(l.uz, l.sd.n[2], sp.uz);
-      be_->sweep(dt_, sp, kspec2_, kCompute);
+      be_->sweep(dt_, sp, kpre, kCompute);
       ++n;
     }
   }
@@ -1405,7 +1435,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
   // is not a multiple of K_), same schedule and buffers, kernel of depth Kp;
   // Kp = K_ + 1: a long sweep (long_sweeps_for: single subdomain, or K+1-deep
   // ghosts with long_halo_), whose exchange and boundary layers are K+1 deep
-  if (Kp <= 0) Kp = K_;
+  if (Kp <= 0) Kp = sweep_depth();
   HEAT3D_CHECK(Kp <= K_ || (Kp == K_ + 1 && (!has_halo_ || long_halo_)),
                "sweep depth " << Kp << " exceeds the halo depth " << K_);
   const int dv = Kp > K_ ? 1 : 0;
@@ -1413,7 +1443,8 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
   const bool lb = dv || (thick && long_halo_);
   H3D_TRACE("sweep" << Kp << " issued=" << issued_ << " buf=" << bi << (capturing_ ? " (capturing)" : ""));
   HEAT3D_CHECK(tb_, "temporal blocking not enabled for this decomposition");
-  HEAT3D_CHECK(!has_cond_, "K-step sweeps have no conductivity form");
+  HEAT3D_CHECK(!has_cond_ || (cond_sweeping() && Kp <= Kc_),
+               "K-step sweeps have no conductivity form (--conductivity-sweeps: tv sweeps up to depth " << Kc_ << ")");
   if (last_kind_ != 2) join_pipeline();
   last_kind_ = 2;
   // lagged schedule: events and residual slots alternate by sweep parity
@@ -1550,7 +1581,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
 }
 
 bool Solver::fused_check() const {
-  return cfg_.fuse_check && be_->is_gpu() && tb_ && !tb_overlap_ && local_.size() == 1 &&
+  return cfg_.fuse_check && be_->is_gpu() && tb_ && !has_cond_ && !tb_overlap_ && local_.size() == 1 &&
          (comm_->all_local() || comm_->size() == 1) && fake_allreduce_us_ <= 0;
 }
 
@@ -1717,9 +1748,9 @@ std::vector<std::pair<std::string, double>> Solver::profile_sweeps(int n) {
   try {
     for (int i = 0; i < n; ++i) {
       prof_idx_ = i;
-      record_segment(issued_, K_, cur());
-      enqueue_multi(cur(), K_);
-      issued_ += K_;
+      record_segment(issued_, sweep_depth(), cur());
+      enqueue_multi(cur(), sweep_depth());
+      issued_ += sweep_depth();
       cur_ = nxt(cur_);
     }
     prof_idx_ = -1;
@@ -1774,7 +1805,7 @@ std::vector<std::pair<std::string, double>> Solver::profile_sweeps(int n) {
     }
   }
   out.push_back({"sweeps", (double)(n - 2)});
-  out.push_back({"steps_per_sweep", (double)K_});
+  out.push_back({"steps_per_sweep", (double)sweep_depth()});
   for (auto& kv : acc) out.push_back({kv.first, kv.second.first / std::max(1, kv.second.second)});
   return out;
 }
@@ -1868,7 +1899,7 @@ void Solver::accumulate_phase_times() {
 // event / residual-slot parity of single steps (2) and of overlapped sweeps (2).
 int Solver::graph_len_for(int64_t n) const {
   int cyc;
-  if (sweeping()) cyc = K_ * (nbuf_ == 3 ? 6 : 2);
+  if (sweeping()) cyc = sweep_depth() * (nbuf_ == 3 ? 6 : 2);
   else cyc = nbuf_ == 3 ? 6 : 2;
   // auto: 32 iterations, 96 for the overlapped multi-stream schedule, whose
   // per-stream graphs start and end joined (each launch drains the halo /
@@ -1880,12 +1911,12 @@ int Solver::graph_len_for(int64_t n) const {
   // a step count shorter than one cycle (the driver's 20-step window at 8
   // ranks: 12 steps in K = 3 sweeps + 2 long sweeps; the 3-buffer cycle is
   // 18) is one graph too, replayable only from the same state
-  if (G == 0 && sweeping()) G = (int)(n - n % K_);
+  if (G == 0 && sweeping()) G = (int)(n - n % sweep_depth());
   return G;
 }
 
 int Solver::long_sweeps_for(int64_t n) const {
-  if (!sweeping() || (has_halo_ && !long_halo_) || !kspec2_.multi_step()) return 0;
+  if (!sweeping() || has_cond_ || (has_halo_ && !long_halo_) || !kspec2_.multi_step()) return 0;
   if (K_ + 1 > 6 || K_ + 1 > kResidualSlots) return 0;
   if (long_major_ && cfg_.long_sweeps) {
     // the most long sweeps b with n - b (K + 1) a multiple of K (b = n mod K
@@ -1987,9 +2018,10 @@ Solver::GraphEntry* Solver::build_graph(int G, int kind_req) {
     }
     last_kind_ = e.kind == 3 ? 2 : e.kind;
     if (e.kind == 2) {
-      for (int i = 0; i < G / K_; ++i) {
+      const int Ks = sweep_depth();
+      for (int i = 0; i < G / Ks; ++i) {
         enqueue_multi(cur_);
-        issued_ += K_;
+        issued_ += Ks;
         cur_ = nxt(cur_);
       }
     } else if (e.kind == 3) {
@@ -2084,9 +2116,10 @@ void Solver::run_chunk(int64_t n) {
         ++graph_launches_;
         if (multi_stream()) sg_unchecked_ = true;
         if (g->kind == 2) {
-          for (int i = 0; i < G / K_; ++i) {
-            record_segment(issued_, K_, cur());
-            issued_ += K_;
+          const int Ks = sweep_depth();
+          for (int i = 0; i < G / Ks; ++i) {
+            record_segment(issued_, Ks, cur());
+            issued_ += Ks;
             cur_ = nxt(cur_);
             if (tb_overlap_) ++nsweep_;  // as enqueue_multi counts them
           }
@@ -2110,7 +2143,7 @@ void Solver::run_chunk(int64_t n) {
     }
     if (sweeping() && n >= 2 && !phase_timing_) {
       // a full sweep, or a partial one for a remainder of 2 .. K-1 steps
-      const int Kp = (int)std::min<int64_t>(n, K_);
+      const int Kp = (int)std::min<int64_t>(n, sweep_depth());
       record_segment(issued_, Kp, cur());
       enqueue_multi(cur(), Kp, nlong > 0 && n == Kp);
       issued_ += Kp;
@@ -2199,12 +2232,13 @@ RunResult Solver::run() {
   int64_t K = std::max(1, cfg_.check_every);
   if (sweeping()) {
     // long-major: chunks of whole K+1-step sweeps too (24 = 6 x 4)
-    const int64_t cyc = (int64_t)K_ * (nbuf_ == 3 ? 6 : 2) * (long_major_ ? K_ + 1 : 1);
+    const int64_t cyc = (int64_t)sweep_depth() * (nbuf_ == 3 ? 6 : 2) * (long_major_ && !has_cond_ ? K_ + 1 : 1);
     if (graphs_allowed()) K = std::max<int64_t>(K, graph_len_for(INT32_MAX));
     K = std::max(cyc, K - K % cyc);
   }
   const std::size_t poll_bytes = cfg_.verbose > 0 ? sizeof(DeviceState) : offsetof(DeviceState, hist);
   int pslot = 0;
+  int64_t poll_issued[2] = {0, 0};  // iterations issued when each poll copy was enqueued
   bool have_prev = false, stop = false;
   int64_t next_ckpt = cfg_.checkpoint_every > 0 ? issued_ + cfg_.checkpoint_every : -1;
   int64_t next_verify = cfg_.verify_halo > 0 ? issued_ + cfg_.verify_halo : -1;
@@ -2223,6 +2257,7 @@ RunResult Solver::run() {
     ev_wait(kReduce, EV_CHK + 0);
     ev_wait(kReduce, EV_CHK + 1);
     be_->copy(&hstate_[pslot], dstate_, poll_bytes, CopyKind::D2H, kReduce);
+    poll_issued[pslot] = issued_;
     ev_record(EV_POLL + pslot, kReduce);
     if (have_prev) {
       const int q = pslot ^ 1;
@@ -2242,7 +2277,13 @@ RunResult Solver::run() {
             std::printf("iteration %lld residual %.6e\n", (long long)it, hs.hist[it % hs.hist_cap]);
         printed = hs.iter;
       }
-      if (hs.done) stop = true;
+      // The copy runs on the reduce stream while the next chunk may already
+      // run on the compute stream (single-subdomain sweeps check there): it can
+      // show a convergence inside that next chunk, or not, by a few
+      // microseconds.  Such a flag is left for the next poll, which shows it
+      // for certain, so that the chunks issued past convergence (and the check
+      // count, which the no-op sweeps advance) do not depend on that timing.
+      if (hs.done && (hs.fault == 2 || hs.conv_iter < poll_issued[q])) stop = true;
       // wall budget (--time-limit): an iteration cap voted at the same chunk
       // on every rank (a per-rank clock test could stop the ranks at
       // different chunks, and the collectives would no longer pair up):

@@ -82,6 +82,7 @@ class Solver {
   int64_t interior_points() const { return (dec_.N[0] - 2) * (dec_.N[1] - 2) * (dec_.N[2] - 2); }
   std::string kernel_name() const {
     const std::string one = kspec_.resolved(cfg_.dtype).str();
+    if (cond_sweeping()) return spec_for_depth(Kc_).str() + "+" + one;
     return sweeping() ? kspec2_.resolved(cfg_.dtype).str() + "+" + one : one;
   }
 
@@ -143,16 +144,19 @@ class Solver {
   // in (0, 1], else every rank throws UsageError.  Each local rank keeps
   // Ch = dtype(0.5 * c) on its owned box plus its full ghost depth, the wall
   // vertices included (a face weight towards a wall reads c there).  While a
-  // conductivity is set every iteration runs as a single step (the K-step
-  // sweep kernels have no conductivity form); the deep ghosts and their
-  // exchange stay.  Setting or clearing behaves like set_source: graphs are
+  // conductivity is set every iteration runs as a single step, unless
+  // Config::cond_sweeps asks for the K-step sweeps of the tv kernel family
+  // (stencil_tbv.hip; depth min(K, the deepest tv kernel built), every
+  // residual, the separate check kernel, no long sweeps, no start-up timing);
+  // the deep ghosts and their exchange stay either way.  Setting or clearing behaves like set_source: graphs are
   // destroyed, the convergence state returns to iteration 0, the field is
   // kept.  Not with --compat.
   void set_conductivity(const double* global_c);
   void set_conductivity_file(const std::string& path);
   void clear_conductivity();
   bool has_conductivity() const { return has_cond_; }
-  // K-step sweeps are what run() / step() issue (temporal blocking on, no conductivity field)
+  // K-step sweeps are what run() / step() issue (temporal blocking on, and no
+  // conductivity field or Config::cond_sweeps)
   bool sweeps_active() const { return sweeping(); }
   void set_field_file(const std::string& path);
 
@@ -294,8 +298,15 @@ class Solver {
   bool initialized_ = false;
   void preflight_source();
   bool has_cond_ = false;
-  // K-step sweeps run (temporal blocking on and no conductivity field)
-  bool sweeping() const { return tb_ && !has_cond_; }
+  // K-step sweeps run (temporal blocking on, and no conductivity field or the
+  // tv sweeps asked for)
+  bool sweeping() const { return tb_ && (!has_cond_ || cond_sweeping()); }
+  // ... of the tv family, with the conductivity field (--conductivity-sweeps)
+  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2; }
+  // steps per sweep of the schedule: K_, or the tv sweeps' depth Kc_ <= K_ (a
+  // sweep shallower than the ghost depth K_ is what a partial sweep is)
+  int sweep_depth() const { return cond_sweeping() ? Kc_ : K_; }
+  int Kc_ = 0;  // min(K_, deepest tv depth built for the dtype); the CPU backend: K_
   void preflight_extra_field(const char* what, std::size_t extra);
   // copies n values of global row (gi, gj) from column gk on
   using GlobalRows = std::function<void(int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst)>;

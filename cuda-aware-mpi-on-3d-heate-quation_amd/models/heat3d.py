@@ -128,7 +128,7 @@ class HeatSolver:
                  kernel: str = "auto", graph: bool = True, overlap: bool = True,
                  check_every: int = 64, graph_chunk: int = 0, device: Optional[int] = None,
                  threads: int = 0, extra_args: Sequence[str] = (), group=None,
-                 phantom: Optional[Sequence[int]] = None):
+                 phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False):
         ext = native()
         self.model = HeatEquation3D(tuple(int(v) for v in n))  # type: ignore[arg-type]
         args: List[str] = [str(int(v)) for v in n] + [str(int(iter_max)), _fmt(eps)]
@@ -146,6 +146,9 @@ class HeatSolver:
             args.append("--no-overlap")
         if threads:
             args += ["--threads", str(threads)]
+        if conductivity_sweeps:
+            # with a conductivity field: K-step sweeps of the tv kernels instead of single steps
+            args.append("--conductivity-sweeps")
         args += list(extra_args)
         self.args = args
 
@@ -253,8 +256,8 @@ class HeatSolver:
         diffusivity of the best-conducting material, so the time step stays
         stable).  A value outside (0, 1] or not finite is the native
         ``UsageError`` (a RuntimeError), raised on every rank.  While set, every
-        iteration runs as a single step: the K-step sweep kernels have no
-        conductivity form.  Keeps the field, restarts the iteration count and
+        iteration runs as a single step, or, with ``conductivity_sweeps=True``,
+        in K-step sweeps of the tv kernels (same bits).  Keeps the field, restarts the iteration count and
         the convergence state at 0.  Collective."""
         c = np.ascontiguousarray(np.asarray(c, dtype=np.float64))
         if c.shape != tuple(self.model.n):

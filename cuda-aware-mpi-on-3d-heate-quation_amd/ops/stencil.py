@@ -168,8 +168,10 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
     GPU tensors run the gfx950 kernel, CPU tensors the K-single-steps
     definition (csrc/kernels/kernels_cpu.cpp).  ``source``: optional heat-source
     field S in the same layout, added at every step.  ``conductivity``: the
-    gfx950 sweep kernels have no conductivity form (RuntimeError); CPU tensors
-    run the K-single-steps definition with it."""
+    field Ch = dtype(0.5 * c) in the same layout; on the GPU it needs a ``tv2``
+    / ``tv3`` kernel (stencil_tbv.hip; the tl kernels have no conductivity form
+    and a tv kernel needs one: RuntimeError either way), CPU tensors run the
+    K-single-steps definition with it."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -189,12 +191,13 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
 
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
            kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0,
-           source: Optional[PaddedField] = None) -> None:
+           source: Optional[PaddedField] = None, conductivity: Optional[PaddedField] = None) -> None:
     """K-step sweep with deep ghosts on every axis (the block-decomposition
     schedule): ``u`` = (ux0, ux1, uy0, uy1, uz0, uz1) are the update ranges of
     the intermediate steps.  GPU tensors run the lean kernel, CPU tensors the
     K-single-steps definition.  ``source``: optional heat-source field S in the
-    same layout (deep ghosts included), added at every step."""
+    same layout (deep ghosts included), added at every step.  ``conductivity``:
+    as in ``sweep`` (GPU: ``tv2`` / ``tv3``)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -205,10 +208,11 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     args = (src.dt, src.data_ptr(), dst.data_ptr(), list(src.n), [src.gx, src.gy, src.gz], list(box), list(u),
             list(D), sptr, slot, kernel)
     qptr = _source_ptr(src, source)
+    cptr = _cond_ptr(src, conductivity)
     if src.device.type == "cuda":
-        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr)
+        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr)
     else:
-        native().cpu.stencil_sweep3(*args, qptr)
+        native().cpu.stencil_sweep3(*args, qptr, cptr)
 
 
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
