@@ -146,6 +146,7 @@ static int drive(const Config& cfg, Solver& solver) {
                           ", " + std::to_string(d.topo.dims[2]) + "]");
     j.set("kernel", solver.kernel_name());
     j.set_bool("conductivity_sweeps", cfg.cond_sweeps);
+    j.set("insulated", insulated_str(cfg.insulated));
     j.set("eps", cfg.eps);
     j.set("iter_max", (int64_t)cfg.iter_max);
     j.set_bool("converged", r.converged);

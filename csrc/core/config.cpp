@@ -49,6 +49,32 @@ Physics Physics::make(int64_t nx, int64_t ny, int64_t nz) {
   return p;
 }
 
+static const char* const kFaceNames[6] = {"x-", "x+", "y-", "y+", "z-", "z+"};
+
+unsigned parse_insulated(const std::string& s) {
+  if (s == "all") return 0x3fu;
+  if (s == "none") return 0u;
+  unsigned mask = 0;
+  std::stringstream ss(s);
+  std::string name;
+  while (std::getline(ss, name, ',')) {
+    int f = -1;
+    for (int i = 0; i < 6; ++i)
+      if (name == kFaceNames[i]) f = i;
+    if (f < 0) throw UsageError("bad --insulated face '" + name + "' (want a list of x-,x+,y-,y+,z-,z+, or all)");
+    mask |= 1u << f;
+  }
+  if (s.empty() || s.back() == ',') throw UsageError("bad --insulated '" + s + "' (want a list of x-,x+,y-,y+,z-,z+, or all)");
+  return mask;
+}
+
+std::string insulated_str(unsigned mask) {
+  std::string out;
+  for (int i = 0; i < 6; ++i)
+    if ((mask >> i) & 1u) out += (out.empty() ? "" : ",") + std::string(kFaceNames[i]);
+  return out.empty() ? "none" : out;
+}
+
 std::array<int, 3> parse_decomp(const std::string& s) {
   std::array<int, 3> d = {0, 0, 0};
   int idx = 0;
@@ -107,6 +133,8 @@ std::string Config::usage() {
      << "                            float64, NX*NY*NZ values, z fastest (the checkpoint field file's order)\n"
      << "  --conductivity FILE       relative conductivity c, 0 < c <= 1 (T_t = div(alpha c grad T) + q), same format\n"
      << "                            as --source; iterations then run as single steps (no K-step sweeps)\n"
+     << "  --insulated FACES         zero-flux (adiabatic) walls: a list of x-,x+,y-,y+,z-,z+ or all; the other\n"
+     << "                            faces stay Dirichlet (not with --compat)\n"
      << "  --conductivity-sweeps     with a conductivity field: K-step sweeps of the tv kernels (tv2 / tv3,\n"
      << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
@@ -256,6 +284,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--initial") c.initial_file = get("--initial");
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
+    else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
     else if (key == "--json-out") c.json_out = get("--json-out");
     else if (key == "--verbose") c.verbose = (int)to_i64(get("--verbose"), "--verbose");
     else if (key == "--progress") c.progress_s = to_f64(get("--progress"), "--progress");
@@ -374,6 +403,8 @@ Config Config::parse(int argc, const char* const* argv) {
     throw UsageError("--source / --initial / --conductivity are not part of --scheme reference");
   if (!c.conductivity_file.empty() && c.compat)
     throw UsageError("--conductivity is not part of --compat (the reference's uniform material)");
+  if (c.insulated && (c.compat || c.scheme == "reference"))
+    throw UsageError("--insulated is not part of --compat / --scheme reference (the reference's Dirichlet walls)");
   if (c.cond_sweeps && c.compat)
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
   return c;

@@ -71,6 +71,9 @@ struct Config {
   bool cond_sweeps = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
+  // --insulated: faces of the global grid that are zero-flux walls instead of
+  // Dirichlet ones, bit 2 * axis + side (x-, x+, y-, y+, z-, z+; parse_insulated)
+  unsigned insulated = 0;
   std::string json_out;
   int verbose = 0;
   double progress_s = 0;          // run(): stderr heartbeat period (0 = off)
@@ -136,5 +139,8 @@ class UsageError : public Error {
 };
 
 std::array<int, 3> parse_decomp(const std::string& s);
+// "x-,x+,z-" | "all" | "none" -> face mask (bit 2 * axis + side); unknown names throw UsageError
+unsigned parse_insulated(const std::string& s);
+std::string insulated_str(unsigned mask);  // the canonical list ("none" for 0)
 
 }  // namespace heat3d

@@ -55,6 +55,32 @@ static inline double row_var(const Real* __restrict in, Real* __restrict out, co
   return nan ? std::nan("") : lres;
 }
 
+template <typename Real>
+static inline double row_wall(const Real* __restrict in, Real* __restrict out, int64_t n, int64_t oxm, int64_t oxp,
+                              int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz) {
+  double lres = 0.0;
+  bool nan = false;
+  for (int64_t k = 0; k < n; ++k) {
+    const Real T = in[k];
+    const Real zm = k == kzm ? T : in[k - 1], zp = k == kzp ? T : in[k + 1];
+    const Real nv = ftcs_update<Real>(T, in[k + oxm], in[k + oxp], in[k + oym], in[k + oyp], zm, zp, Dx, Dy, Dz);
+    out[k] = nv;
+    const double d = resid_abs(nv, T);
+    nan |= d != d;
+    lres = d > lres ? d : lres;
+  }
+  return nan ? std::nan("") : lres;
+}
+
+double ftcs_row_wall_f64(const double* in, double* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym, int64_t oyp,
+                         int64_t kzm, int64_t kzp, double Dx, double Dy, double Dz) {
+  return row_wall<double>(in, out, n, oxm, oxp, oym, oyp, kzm, kzp, Dx, Dy, Dz);
+}
+double ftcs_row_wall_f32(const float* in, float* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym, int64_t oyp,
+                         int64_t kzm, int64_t kzp, float Dx, float Dy, float Dz) {
+  return row_wall<float>(in, out, n, oxm, oxp, oym, oyp, kzm, kzp, Dx, Dy, Dz);
+}
+
 double ftcs_row_f64(const double* in, double* out, int64_t n, int64_t sx, int64_t sy, double Dx, double Dy,
                     double Dz) {
   return row<double, false>(in, out, nullptr, n, sx, sy, Dx, Dy, Dz);
@@ -90,10 +116,11 @@ const RowKernels& cpu_row_kernels() {
     __builtin_cpu_init();
     if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"))
       return RowKernels{rows_fma::ftcs_row_f64, rows_fma::ftcs_row_f32, "x86-64+fma+avx2", rows_fma::ftcs_row_src_f64,
-                        rows_fma::ftcs_row_src_f32, rows_fma::ftcs_row_var_f64, rows_fma::ftcs_row_var_f32};
+                        rows_fma::ftcs_row_src_f32, rows_fma::ftcs_row_var_f64, rows_fma::ftcs_row_var_f32,
+                        rows_fma::ftcs_row_wall_f64, rows_fma::ftcs_row_wall_f32};
     return RowKernels{rows_generic::ftcs_row_f64, rows_generic::ftcs_row_f32, "x86-64 (libm fma)",
                       rows_generic::ftcs_row_src_f64, rows_generic::ftcs_row_src_f32, rows_generic::ftcs_row_var_f64,
-                      rows_generic::ftcs_row_var_f32};
+                      rows_generic::ftcs_row_var_f32, rows_generic::ftcs_row_wall_f64, rows_generic::ftcs_row_wall_f32};
   }();
   return k;
 }

@@ -31,6 +31,13 @@ template <typename Real>
 using FtcsRowVarFn = double (*)(const Real* in, Real* out, const Real* cond, const Real* src, int64_t n, int64_t sx,
                                 int64_t sy, Real Dx, Real Dy, Real Dz);
 
+// insulated walls (StencilParams::wall): om / op are the offsets of the x and
+// y neighbours (0 where the neighbour across a wall is replaced by the centre
+// value), kzm / kzp the row indices whose z- / z+ neighbour is (-1: none)
+template <typename Real>
+using FtcsRowWallFn = double (*)(const Real* in, Real* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym,
+                                 int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz);
+
 struct RowKernels {
   FtcsRowFn<double> f64;
   FtcsRowFn<float> f32;
@@ -39,6 +46,8 @@ struct RowKernels {
   FtcsRowSrcFn<float> src_f32;
   FtcsRowVarFn<double> var_f64;
   FtcsRowVarFn<float> var_f32;
+  FtcsRowWallFn<double> wall_f64;
+  FtcsRowWallFn<float> wall_f32;
 };
 
 const RowKernels& cpu_row_kernels();
@@ -52,6 +61,10 @@ double ftcs_row_var_f64(const double*, double*, const double*, const double*, in
                         double, double);
 double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
                         float);
+double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double,
+                         double, double);
+double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
+                         float, float);
 }  // namespace rows_generic
 namespace rows_fma {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
@@ -62,6 +75,10 @@ double ftcs_row_var_f64(const double*, double*, const double*, const double*, in
                         double, double);
 double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
                         float);
+double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double,
+                         double, double);
+double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
+                         float, float);
 }  // namespace rows_fma
 
 }  // namespace cpu

@@ -45,6 +45,9 @@ struct KernelSpec {
   KernelSpec resolved(DType t) const;
 };
 
+// StencilParams::wall: no insulated wall on this side
+constexpr int64_t kNoWall = -(int64_t(1) << 40);
+
 struct StencilParams {
   const void* in = nullptr;
   void* out = nullptr;
@@ -87,6 +90,24 @@ struct StencilParams {
   // single-step kernels and the tv sweeps have a conductivity form (a tl sweep
   // with it is an error, as is a tv sweep without it).
   const void* cond = nullptr;
+  // Insulated (zero-flux) walls: wall[a][0] / wall[a][1] is the local
+  // coordinate along axis a of the updated plane (row, column) next to the
+  // insulated low / high wall of the global grid, kNoWall where that face is
+  // Dirichlet or lies outside what this rank can reach.  At such a point the
+  // neighbour across the wall is replaced by the centre value (the mirror
+  // ghost; the flux through the face between them is exactly 0) and the update
+  // is evaluated as ever.  Taken from global indices, so it also holds for
+  // wall-adjacent points computed inside a neighbour's deep halo.  cpu::stencil
+  // and cpu::stencil_multi honour it (without source / conductivity: those run
+  // as single steps on wall planes copied from their inward neighbours), as do
+  // the wall forms of the lean sweep (stencil_tbl_wall.hip); the single-step
+  // gfx950 kernels do not take it.
+  int64_t wall[3][2] = {{kNoWall, kNoWall}, {kNoWall, kNoWall}, {kNoWall, kNoWall}};
+  bool has_walls() const {
+    for (int a = 0; a < 3; ++a)
+      if (wall[a][0] != kNoWall || wall[a][1] != kNoWall) return true;
+    return false;
+  }
 };
 
 struct InitParams {
@@ -152,7 +173,10 @@ bool lean_pair_supported(DType t, const KernelSpec& k);
 int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, int U, int L, int esize);
 // Is the lean kernel variant that k resolves to for dtype t instantiated?
 // with_source: its heat-source form (StencilParams::src != nullptr)
-bool lean_supported(DType t, const KernelSpec& k, bool with_source = false);
+// with_walls: its insulated-wall form (StencilParams::has_walls; no source form)
+bool lean_supported(DType t, const KernelSpec& k, bool with_source = false, bool with_walls = false);
+// the wall forms' dispatch (stencil_tbl_wall.hip); p == nullptr: only report
+bool lean_wall_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
 // K-step sweep with a conductivity field (stencil_tbv.hip; spec tvK): needs
 // p.cond, honours p.src; no fused check, no schedule tuning
 void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);

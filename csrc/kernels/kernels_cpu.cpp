@@ -82,6 +82,15 @@ static void stencil_t(const StencilParams& p) {
     if constexpr (sizeof(Real) == 8) return cpu_row_kernels().var_f64;
     else return cpu_row_kernels().var_f32;
   }();
+  const auto rowwall = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().wall_f64;
+    else return cpu_row_kernels().wall_f32;
+  }();
+  // insulated walls (StencilParams::wall): the uniform update only
+  const bool walls = p.has_walls();
+  HEAT3D_CHECK(!walls || (!p.src && !p.cond),
+               "cpu::stencil: insulated walls with a source or a conductivity run as single steps on copied wall "
+               "planes, not through StencilParams::wall");
   const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
   const Real* __restrict cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
   const int64_t nk = b.extent(2);
@@ -91,6 +100,9 @@ static void stencil_t(const StencilParams& p) {
       const int64_t c = L.index(i, j, b.lo[2]);
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
       const double lres = nk <= 0 ? 0.0
+                          : walls ? rowwall(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
+                                            j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
+                                            p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], Dx, Dy, Dz)
                           : cond  ? rowvar(in + c, out + c, cond + c, src ? src + c : nullptr, nk, sx, sy, Dx, Dy, Dz)
                           : src   ? rowsrc(in + c, out + c, src + c, nk, sx, sy, Dx, Dy, Dz)
                                   : rowfn(in + c, out + c, nk, sx, sy, Dx, Dy, Dz);

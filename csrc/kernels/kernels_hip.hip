@@ -593,6 +593,9 @@ static void dispatch_tile(const StencilParams& p, const KernelSpec& ks, hipStrea
 
 void stencil(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   if (p.box.empty()) return;
+  // (never Dirichlet arithmetic next to an insulated wall)
+  HEAT3D_CHECK(!p.has_walls(), "the single-step kernels take no StencilParams::wall: copy the wall planes from their "
+                               "inward neighbours before the step (Solver::refresh_walls)");
   if (p.cond) return stencil_var(t, p, k, stream);  // conductivity forms (stencil_var.hip)
   if (k.kind == KernelSpec::Naive) {
     if (t == DType::F64) launch_naive<double>(p, S(stream));

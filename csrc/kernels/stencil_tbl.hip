@@ -220,7 +220,9 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   return false;
 }
 
-bool lean_supported(DType t, const KernelSpec& k, bool with_source) {
+bool lean_supported(DType t, const KernelSpec& k, bool with_source, bool with_walls) {
+  // (walls with a source run as single steps: no sweep form)
+  if (with_walls) return !with_source && k.kind == KernelSpec::TBL && lean_wall_dispatch(t, nullptr, k, nullptr);
   if (with_source)
     return t == DType::F64 ? dispatch_tbl_src<double>(nullptr, k, nullptr) : dispatch_tbl_src<float>(nullptr, k, nullptr);
   return t == DType::F64 ? dispatch_tbl<double>(nullptr, k, nullptr) : dispatch_tbl<float>(nullptr, k, nullptr);
@@ -229,6 +231,18 @@ bool lean_supported(DType t, const KernelSpec& k, bool with_source) {
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   refuse_conductivity(p, k);
   if (p.box.empty()) return;
+  if (p.has_walls()) {
+    // a sweep next to an insulated wall never falls back to Dirichlet arithmetic
+    const bool ok = !p.src && lean_wall_dispatch(t, &p, k, stream);
+    if (!ok) {
+      const KernelSpec r = k.resolved(t);
+      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t)
+                                        << ") has no insulated-wall form" << (p.src ? " with a heat source" : "")
+                                        << "; with insulated walls use the default --kernel2 (tl2, tl3 or tl4 "
+                                           "without shape fields)");
+    }
+    return;
+  }
   if (p.src) {
     const bool ok =
         t == DType::F64 ? dispatch_tbl_src<double>(&p, k, S(stream)) : dispatch_tbl_src<float>(&p, k, S(stream));
@@ -256,6 +270,11 @@ void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
 
 // (every K-step launch comes through stencil_lean or stencil_lean_pair)
 void refuse_conductivity(const StencilParams& p, const KernelSpec& k) {
+  // nor do the pair kernel (spec field V = 2, asked for by name: with walls an
+  // unset V means 1 for either dtype) and the tv kernels have a wall form;
+  // stencil_lean goes on to the lean kernel's wall forms after this check
+  if (p.has_walls() && (k.kind == KernelSpec::TBV || k.V == 2 || p.cond))
+    HEAT3D_THROW("K-step sweep kernel " << k.str() << " has no insulated-wall form");
   if (p.cond)
     HEAT3D_THROW("K-step sweep kernel " << k.str() << " has no conductivity form: with a conductivity field every "
                                                      "iteration runs as a single step (tile | naive)");

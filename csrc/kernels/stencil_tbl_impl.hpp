@@ -82,6 +82,15 @@ struct TBLArgs {
   int fslot, fblocks;          // its first residual slot and the grid's workgroup count
 };
 
+// Insulated walls in the kernel's frame (x the marching axis, y the tile rows,
+// z the lanes): the coordinate of the wall-adjacent plane / row / column, or
+// a sentinel no coordinate reaches (kWallNoneLo below everything on the low
+// side, kWallNoneHi above everything on the high side)
+struct TBLWalls {
+  int x[2], y[2], z[2];
+};
+constexpr int kWallNoneLo = -(1 << 30), kWallNoneHi = 1 << 30;
+
 namespace {
 
 constexpr int gcd_l(int a, int b) { return b == 0 ? a : gcd_l(b, a % b); }
@@ -147,6 +156,7 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 // tuned schedules.
 #define H3D_TBL_NAME stencil_tbl
 #define H3D_TBL_SRC 0
+#define H3D_TBL_WALL 0
 #include "stencil_tbl_kernel.inc"
 #undef H3D_TBL_NAME
 #undef H3D_TBL_SRC
@@ -155,18 +165,44 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 #include "stencil_tbl_kernel.inc"
 #undef H3D_TBL_NAME
 #undef H3D_TBL_SRC
+#undef H3D_TBL_WALL
+// WALL: insulated (zero-flux) walls (kernels.hpp StencilParams::wall).  At an
+// updated point next to an insulated wall the neighbour across it is replaced
+// by the centre value before the update, at every stage: a deep mirrored ghost
+// would not do, because fma(-2, c, xp) + xm is not symmetric in xm and xp and
+// mirrored points would differ in the last bit from single steps.  The
+// substitution lives in the masked step only: per stage a uniform compare of
+// its plane for the marching axis, two bits per row in an SGPR for the rows, a
+// lane mask for z (constant over the piece).  Waves, tiles and plane steps
+// that hold a wall-adjacent row, column or plane are kept off the mask-free
+// step (wfast, zfast, xf_lo / xf_hi), which is therefore the code of the
+// uniform kernel; no register row is added.  A kernel of its own
+// (stencil_tbl_wall, instantiated in stencil_tbl_wall.hip), so the kernels
+// without walls keep their code, names and tuned schedules.
+#define H3D_TBL_NAME stencil_tbl_wall
+#define H3D_TBL_SRC 0
+#define H3D_TBL_WALL 1
+#include "stencil_tbl_kernel.inc"
+#undef H3D_TBL_NAME
+#undef H3D_TBL_SRC
+#undef H3D_TBL_WALL
 
 // EW: the edge role of waves 0 and WY - 1 (0 = off, else 1 + their owned rows)
-template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false, int EW = 0>
+// WALL: the insulated-wall form (p.wall; no source form, no edge role)
+template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false, int EW = 0,
+          bool WALL = false>
 void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
   constexpr bool swap_xy = SW;
   // (if constexpr: only the form that is launched gets instantiated)
   const void* kfn = [] {
     if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
+    else if constexpr (WALL) return reinterpret_cast<const void*>(&stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>);
     else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>);
   }();
   static_assert(EW == 0 || !SRC, "the edge role has no source form");
+  static_assert(!WALL || (!SRC && EW == 0), "the wall form has no source form and no edge role");
   HEAT3D_CHECK(SRC == (p.src != nullptr), "tl: source form mismatch");
+  HEAT3D_CHECK(WALL == p.has_walls(), "tl: wall form mismatch");
   Box b = p.box;
   constexpr int TY = WY * R + 2 * (EW > 0 ? EW - 1 : 0);  // as the kernel's
   // swap_xy: march along y with x as the tile rows (thin x slabs: a tile of
@@ -214,6 +250,20 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
                "tl: y/z update range outside the ghosted layout");
   HEAT3D_CHECK(g.ulo - 1 >= g.xlo_live && g.uhi <= g.xhi_live + 1 && g.ulo <= b.lo[0] && g.uhi >= b.hi[0],
                "tl: u range [" << g.ulo << "," << g.uhi << ") outside the ghosted layout");
+  // the walls in the kernel's frame (swap_xy relabels x and y as it does the box)
+  TBLWalls wl{};
+  {
+    auto coord = [](int64_t v, int side) {
+      const int none = side ? kWallNoneHi : kWallNoneLo;
+      return v == kNoWall || v <= kWallNoneLo || v >= kWallNoneHi ? none : (int)v;
+    };
+    const int ax = swap_xy ? 1 : 0, ay = swap_xy ? 0 : 1;
+    for (int e = 0; e < 2; ++e) {
+      wl.x[e] = coord(p.wall[ax][e], e);
+      wl.y[e] = coord(p.wall[ay][e], e);
+      wl.z[e] = coord(p.wall[2][e], e);
+    }
+  }
   constexpr int YS = TY - 2 * K;
   static const int slots = device_slots(kfn, 64 * WY);  // magic static: thread-safe under --gpus N
   constexpr int U = Q == 4 ? 12 : 6;  // the kernel's unroll (lcm(Q, 3, 2))
@@ -265,6 +315,10 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       hipLaunchKernelGGL((stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
                          static_cast<const Real*>(p.in), static_cast<Real*>(p.out), static_cast<const Real*>(p.src),
                          ga, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
+    else if constexpr (WALL)
+      hipLaunchKernelGGL((stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
+                         static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, wl, (Real)p.D[0],
+                         (Real)p.D[1], (Real)p.D[2], r, done);
     else
     hipLaunchKernelGGL((stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
                        s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, (Real)p.D[0], (Real)p.D[1],
@@ -279,7 +333,9 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       const int wide = 64 - 2 * K, aligned = sizeof(Real) == 8 ? wide & ~7 : wide;
       for (int z : {wide, aligned})
         if (std::find(zs_opts.begin(), zs_opts.end(), z) == zs_opts.end()) zs_opts.push_back(z);
-      tune_schedule(SRC ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src") : sizeof(Real) == 8 ? "tl-fp64" : "tl-fp32",
+      tune_schedule(SRC    ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src")
+                    : WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall" : "tl-fp32-wall")
+                    : sizeof(Real) == 8 ? "tl-fp64" : "tl-fp32",
                     kfn, box, slots, p.cu_reserved, U, zs_opts, s, fire,
                     g.nyb, 2 * (K - 1));
       return;  // every candidate computed this sweep

@@ -2,7 +2,11 @@
 // stencil_tbl_impl.hpp once per form: H3D_TBL_NAME stencil_tbl with
 // H3D_TBL_SRC 0, and stencil_tbl_src with H3D_TBL_SRC 1 (heat source, see the
 // comment there).  Textual inclusion keeps the kernel without a source exactly
-// the code it was before the source form existed.
+// the code it was before the source form existed.  H3D_TBL_WALL 1 (kernel
+// stencil_tbl_wall, stencil_tbl_wall.hip) is the insulated-wall form: in the
+// masked step a neighbour across an insulated wall is replaced by the centre
+// value (impl.hpp), and a wave or plane step that holds a wall-adjacent row,
+// column or plane never takes the mask-free step.
 //
 // EW > 0: the edge role (impl.hpp, third step form).  Waves 0 and WY - 1 hold
 // the tile's K halo rows and E = EW - 1 owned rows next to them (R + E rows; the
@@ -13,7 +17,11 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
 #if H3D_TBL_SRC
                                                        const Real* __restrict__ src,
 #endif
-                                                       TBLArgs g, Real Dx, Real Dy, Real Dz,
+                                                       TBLArgs g,
+#if H3D_TBL_WALL
+                                                       TBLWalls wa,
+#endif
+                                                       Real Dx, Real Dy, Real Dz,
                                                        unsigned long long* res, const int* done) {
   static_assert(K >= 2 && K <= 6, "temporal depth");
   // T^n ring: Q = 3 loads plane x+2 into the slot stage 0 frees at step x
@@ -24,6 +32,9 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   constexpr int E = EDGE ? EW - 1 : 0;  // owned rows of an edge wave
   constexpr int RB = R + E;             // rows of an edge wave (register rows of every wave)
   static_assert(!EDGE || (R >= K && WY >= 3 && !SW && !H3D_TBL_SRC), "edge role: halo-only waves, no source form");
+#if H3D_TBL_WALL
+  static_assert(!EDGE && !H3D_TBL_SRC, "the wall form has no edge role and no source form");
+#endif
   constexpr int TY = WY * R + 2 * E;
   constexpr int YS = TY - 2 * K;   // tile stride along y (stored rows)
   // x-loop unroll making every ring index and the LDS parity static
@@ -99,6 +110,29 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   const int64_t sx = g.sx;
 
   // ---- uniform (per wave) classification
+#if H3D_TBL_WALL
+  // ... and holds no wall-adjacent column / row: those take the masked step
+  const bool zfast = c0 >= g.uzlo && c0 + 64 <= g.uzhi && !(wa.z[0] >= c0 && wa.z[0] < c0 + 64) &&
+                     !(wa.z[1] >= c0 && wa.z[1] < c0 + 64);
+  const bool wrows = tr0 >= K && tr0 + R <= TY - K && yb >= g.uylo && yb + R <= g.uyhi &&
+                     yb >= g.blo[1] && yb + R <= g.bhi[1] && !(wa.y[0] >= yb && wa.y[0] < yb + R) &&
+                     !(wa.y[1] >= yb && wa.y[1] < yb + R);
+  const bool wfast = zfast && wrows;
+  // steps whose every stage is valid, updated, counted and (last stage) stored,
+  // and none of whose stages' planes x - s is wall-adjacent (nothing is updated
+  // below the low wall's plane or above the high wall's)
+  const int xf_lo = max(max(max(x0 + 2 * (K - 1), g.ulo + K - 1), g.blo[0] + K - 1), wa.x[0] + K);
+  const int xf_hi = min(min(min(xlast, g.uhi - 1), g.bhi[0] + K - 2), wa.x[1] - 1);
+  // rows of this wave next to the low (bit r) / high (bit RB + r) wall
+  static_assert(2 * RB <= 32, "wall row bits");
+  unsigned wyb = 0;
+#pragma unroll
+  for (int r = 0; r < RB; ++r) {
+    if (yb + r == wa.y[0]) wyb |= 1u << r;
+    if (yb + r == wa.y[1]) wyb |= 1u << (RB + r);
+  }
+  wyb = (unsigned)sgpr((int)wyb);
+#else
   const bool zfast = c0 >= g.uzlo && c0 + 64 <= g.uzhi;
   const bool wrows = tr0 >= K && tr0 + R <= TY - K && yb >= g.uylo && yb + R <= g.uyhi &&
                      yb >= g.blo[1] && yb + R <= g.bhi[1];
@@ -106,6 +140,7 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   // steps whose every stage is valid, updated, counted and (last stage) stored
   const int xf_lo = max(max(x0 + 2 * (K - 1), g.ulo + K - 1), g.blo[0] + K - 1);
   const int xf_hi = min(min(xlast, g.uhi - 1), g.bhi[0] + K - 2);
+#endif
 
   // masked form, per row r (uniform, one SGPR): bit r = row in the update
   // range, bit R + r = stored row, bit 2R + s*R + r = row counted at stage s
@@ -134,6 +169,10 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   // per-lane masks (constant over the piece)
   const bool zin = col >= g.uzlo && col < g.uzhi;
   const bool zst = lane >= K && lane < K + zs && col >= g.blo[2] && col < g.bhi[2];
+#if H3D_TBL_WALL
+  // lanes next to the low / high z wall
+  const bool zwm = col == wa.z[0], zwp = col == wa.z[1];
+#endif
 
   // ---- addressing: uniform base of row yb, column c0; clamped row offsets
   // (uniform by construction: kernel arguments and the readfirstlane'd wave
@@ -246,9 +285,32 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         xcnt = xin && x >= x0 + 2 * s && x <= xlast && p >= g.blo[0] - (K - 1 - s) && p < g.bhi[0] + (K - 1 - s);
         xst = p >= xa && p < xe;
       }
+#if H3D_TBL_WALL
+      // this stage's plane is next to the low / high wall of the marching axis
+      const bool wxm = !FAST && p == wa.x[0], wxp = !FAST && p == wa.x[1];
+#endif
 #pragma unroll
       for (int r = 0; r < NR; ++r) {
         if (!live(r, s)) continue;
+#if H3D_TBL_WALL
+        Real ym = r == 0 ? lo : C[r > 0 ? r - 1 : 0];
+        Real yp = r == NR - 1 ? hi : C[r + 1 < NR ? r + 1 : 0];
+        Real zm = dpp_shr1z(C[r]);
+        Real zp = dpp_shl1z(C[r]);
+        Real xm = M[r], xp = P[r];
+        if constexpr (!FAST) {
+          // the mirror ghost: the neighbour across an insulated wall is the centre value
+          if (wxm) xm = C[r];
+          if (wxp) xp = C[r];
+          if ((wyb >> r) & 1) ym = C[r];
+          if ((wyb >> (RB + r)) & 1) yp = C[r];
+          zm = zwm ? C[r] : zm;
+          zp = zwp ? C[r] : zp;
+        }
+        // (SW: the rows are the x terms of the update, the marching axis its y terms)
+        const Real nv = SW ? ftcs<Real>(C[r], ym, yp, xm, xp, zm, zp, Dx, Dy, Dz)
+                           : ftcs<Real>(C[r], xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);
+#else
         const Real ym = r == 0 ? lo : C[r > 0 ? r - 1 : 0];
         const Real yp = r == NR - 1 ? hi : C[r + 1 < NR ? r + 1 : 0];
         const Real zm = dpp_shr1z(C[r]);
@@ -261,6 +323,7 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
 #else
         const Real nv = SW ? ftcs<Real>(C[r], ym, yp, M[r], P[r], zm, zp, Dx, Dy, Dz)
                            : ftcs<Real>(C[r], M[r], P[r], ym, yp, zm, zp, Dx, Dy, Dz);
+#endif
 #endif
         const Real d = resid_abs_r(nv, C[r]);
         bool upd = true, cnt = true, st = true;

@@ -564,6 +564,7 @@ bool lean_pair_supported(DType t, const KernelSpec& k) {
 
 void stencil_lean_pair(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   refuse_conductivity(p, k);
+  HEAT3D_CHECK(!p.has_walls(), "K-step sweep kernel " << k.str() << " (pairs) has no insulated-wall form");
   if (p.box.empty()) return;
   const bool ok = t == DType::F64 ? run_tbp<double>(&p, k, S(stream)) : run_tbp<float>(&p, k, S(stream));
   if (!ok) {

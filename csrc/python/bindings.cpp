@@ -128,6 +128,13 @@ std::unique_ptr<Solver> create_solver(const std::vector<std::string>& args, int 
 
 DType dt_of(const std::string& s) { return parse_dtype(s); }
 
+// walls = (x-, x+, y-, y+, z-, z+): local coordinate of the wall-adjacent plane, NO_WALL where none
+constexpr std::array<int64_t, 6> kNoWalls = {kNoWall, kNoWall, kNoWall, kNoWall, kNoWall, kNoWall};
+void set_walls(StencilParams& p, const std::array<int64_t, 6>& w) {
+  for (int a = 0; a < 3; ++a)
+    for (int e = 0; e < 2; ++e) p.wall[a][e] = w[2 * a + e];
+}
+
 StencilParams sparams(int64_t in_ptr, int64_t out_ptr, const std::array<int64_t, 3>& n,
                       int64_t esize, const std::array<int64_t, 6>& box,
                       const std::array<double, 3>& D, int64_t state_ptr, int slot) {
@@ -218,6 +225,12 @@ PYBIND11_MODULE(_heat3d, m) {
   });
   // is the lean sweep variant the spec resolves to for dtype instantiated (with_source:
   // its heat-source form)?  No device access (tests/test_lean_variants_cpu.py)
+  m.attr("NO_WALL") = (int64_t)kNoWall;
+  m.def("parse_insulated", &parse_insulated);
+  m.def("insulated_str", &insulated_str);
+  m.def("lean_wall_supported", [](const std::string& dtype, const std::string& spec) {
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true);
+  }, py::arg("dtype"), py::arg("spec"));
   m.def("lean_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
     const heat3d::KernelSpec k = heat3d::KernelSpec::parse(spec);
     if (!k.multi_step()) throw UsageError("lean_supported needs a tl2..tl6 kernel");
@@ -512,7 +525,8 @@ PYBIND11_MODULE(_heat3d, m) {
   hk.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                              int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
+                              int64_t stream, int64_t src_ptr, int64_t cond_ptr,
+                              std::array<int64_t, 6> walls) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -523,12 +537,13 @@ PYBIND11_MODULE(_heat3d, m) {
     }
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    set_walls(p, walls);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
-     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
   hk.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h, int64_t stream) {
     DType t = dt_of(dt);
@@ -565,15 +580,17 @@ PYBIND11_MODULE(_heat3d, m) {
   py::module_ ck = m.def_submodule("cpu", "OpenMP host kernels on host pointers");
   ck.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
-                       int64_t src_ptr, int64_t cond_ptr) {
+                       int64_t src_ptr, int64_t cond_ptr,
+                              std::array<int64_t, 6> walls) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    set_walls(p, walls);
     py::gil_scoped_release nogil;
     cpu::stencil(t, p);
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
-     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
   ck.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
@@ -595,7 +612,8 @@ PYBIND11_MODULE(_heat3d, m) {
   ck.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                              int64_t src_ptr, int64_t cond_ptr) {
+                              int64_t src_ptr, int64_t cond_ptr,
+                              std::array<int64_t, 6> walls) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -606,13 +624,14 @@ PYBIND11_MODULE(_heat3d, m) {
     }
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    set_walls(p, walls);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
     py::gil_scoped_release nogil;
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
-     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
   ck.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h) {
     DType t = dt_of(dt);
@@ -715,6 +734,7 @@ PYBIND11_MODULE(_heat3d, m) {
         d["fault"] = h.fault;
         return d;
       })
+      .def("residual_history", &Solver::residual_history)
       .def("compute_error", [](Solver& s) {
         double g = 0, l = 0;
         s.compute_error(&g, &l);
@@ -786,6 +806,7 @@ PYBIND11_MODULE(_heat3d, m) {
       })
       .def_property_readonly("has_conductivity", &Solver::has_conductivity)
       .def_property_readonly("sweeps_active", &Solver::sweeps_active)
+      .def_property_readonly("sweeps_overlapped", &Solver::sweeps_overlapped)
       .def_property_readonly("has_source", &Solver::has_source)
       .def("inject", &Solver::inject, py::arg("idx"), py::arg("i"), py::arg("j"), py::arg("k"),
            py::arg("value"), py::arg("previous") = false)

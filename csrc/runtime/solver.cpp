@@ -236,7 +236,13 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
     kspec2_.kind = KernelSpec::TBL;
     kspec2_.K = k2;
   }
-  overlap_ = cfg_.overlap;
+  walls_ = cfg_.insulated & 0x3fu;
+  // Single steps next to insulated walls refresh the wall planes first, on
+  // the one stream that then runs the halo and the step: the single-step
+  // schedule of a wall run is not overlapped.  The sweeps are (tb_overlap_
+  // below follows --no-overlap alone): they substitute in the kernel and
+  // need no refresh.
+  overlap_ = cfg_.overlap && !walls_;
 
   // K-step temporal blocking: on by default on the GPU, opt-in on the CPU
   // backend (tests).  Depth K from --temporal K, else from --kernel2 tlK,
@@ -278,7 +284,7 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
   // of every split axis; otherwise exchange first, then sweep
   bool thick = true;
   for (int a = 0; a < 3; ++a) thick &= dims[a] == 1 || min_n[a] >= 2 * K + 1;
-  tb_overlap_ = tb_ && dims[0] * dims[1] * dims[2] > 1 && overlap_ && thick && (!block || cfg_.block_overlap);
+  tb_overlap_ = tb_ && dims[0] * dims[1] * dims[2] > 1 && cfg_.overlap && thick && (!block || cfg_.block_overlap);
   // lagged convergence check (third buffer, two residual-slot banks) keeps
   // the all-reduce + check off the critical path of the overlapped sweeps
   if (cfg_.lag == 1 && !(tb_overlap_ && 2 * K_ <= kResidualSlots))
@@ -307,7 +313,7 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
       KernelSpec ks;
       ks.kind = kspec2_.kind;
       ks.K = K + 1;
-      ok = hip::lean_supported(dt_, ks, has_source_);
+      ok = lean_ok(ks);
     }
     long_halo_ = ok;
     if (long_halo_)
@@ -433,6 +439,10 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
           boundary->push_back(b);
         }
     };
+    for (int a = 0; a < 3; ++a) {
+      if ((walls_ >> (2 * a)) & 1u) l.wall[a][0] = 1 - l.sd.gstart[a];
+      if ((walls_ >> (2 * a + 1)) & 1u) l.wall[a][1] = dec_.N[a] - 2 - l.sd.gstart[a];
+    }
     pieces(K_, &l.tb_interior, &l.tb_boundary);
     if (long_halo_) {
       pieces(K_ + 1, &l.tb_interior_long, &l.tb_boundary_long);
@@ -535,6 +545,45 @@ void Solver::preflight_extra_field(const char* what, std::size_t extra) {
                    << " GB are free");
   }
   planned_bytes_ += extra;
+}
+
+bool Solver::lean_ok(const KernelSpec& ks) const { return hip::lean_supported(dt_, ks, has_source_, walls_ != 0); }
+
+void Solver::set_walls(StencilParams& sp, const Local& l) const {
+  for (int a = 0; a < 3; ++a)
+    for (int e = 0; e < 2; ++e) sp.wall[a][e] = l.wall[a][e];
+}
+
+void Solver::refresh_walls(int b, StreamId s) {
+  if (!walls_) return;
+  for (auto& l : local_)
+    for (int a = 0; a < 3; ++a)
+      for (int e = 0; e < 2; ++e) {
+        if (l.wall[a][e] == kNoWall) continue;
+        const int64_t from = l.wall[a][e], to = e ? from + 1 : from - 1;
+        // both planes inside this rank's allocation (its own wall, or one its deep halo reaches)
+        const int64_t ga = a == 0 ? l.L.gx : a == 1 ? l.L.gy : l.L.gz;
+        if (std::min(from, to) < -ga || std::max(from, to) >= l.sd.n[a] + ga) continue;
+        Box bs, bd;
+        bool empty = false;
+        for (int c = 0; c < 3; ++c) {
+          if (c == a) {
+            bs.lo[c] = from;
+            bd.lo[c] = to;
+            bs.hi[c] = from + 1;
+            bd.hi[c] = to + 1;
+            continue;
+          }
+          // the local extent inside the global grid, less the planes of Dirichlet faces
+          const int64_t gc = c == 0 ? l.L.gx : c == 1 ? l.L.gy : l.L.gz;
+          const int64_t glo = ((walls_ >> (2 * c)) & 1u) ? 0 : 1;
+          const int64_t ghi = dec_.N[c] - (((walls_ >> (2 * c + 1)) & 1u) ? 0 : 1);
+          bs.lo[c] = bd.lo[c] = std::max(-gc, glo - l.sd.gstart[c]);
+          bs.hi[c] = bd.hi[c] = std::min(l.sd.n[c] + gc, ghi - l.sd.gstart[c]);
+          empty |= bs.hi[c] <= bs.lo[c];
+        }
+        if (!empty) be_->copy_box(dt_, l.field[b], l.L, bs, l.field[b], l.L, bd, s);
+      }
 }
 
 bool Solver::is_root() const {
@@ -659,7 +708,7 @@ void Solver::retune() {
   for (bool& b : rl_d_) b = false;
   // a conductivity field: single steps, or the tv sweeps (one shape per
   // depth, every residual): nothing to time
-  if (has_cond_) return;
+  if (has_cond_ || walls_single()) return;
   tune_schedules();
   calibrate_remainders();
   // the sweep form is final: its last-residual variant, where one exists
@@ -671,7 +720,7 @@ void Solver::retune() {
       const bool picked = (rl_pick_[Kp].O & kResidualLastOnly) != 0;
       ks_last_[Kp] = picked ? rl_pick_[Kp] : last_only(spec_for_depth(Kp));
       // (block decompositions: long sweeps keep every residual, see long_major_)
-      rl_d_[Kp] = hip::lean_supported(dt_, ks_last_[Kp], has_source_) && !(ordered_halo_ && Kp > K_);
+      rl_d_[Kp] = lean_ok(ks_last_[Kp]) && !(ordered_halo_ && Kp > K_);
     }
   rl_ = rl_d_[K_];
 }
@@ -885,7 +934,7 @@ void Solver::tune_schedules() {
     KernelSpec ks;
     ks.kind = kspec2_.kind;
     ks.K = K_ + 1;
-    if (hip::lean_supported(dt_, ks, has_source_)) specs.push_back(ks);
+    if (lean_ok(ks)) specs.push_back(ks);
   }
   // the last-residual variants of those: kernels of their own, whose
   // schedules are timed (and looked up) separately
@@ -893,7 +942,7 @@ void Solver::tune_schedules() {
     const std::size_t nf = specs.size();
     for (std::size_t i = 0; i < nf; ++i) {
       const KernelSpec r = last_only(specs[i]);
-      if (hip::lean_supported(dt_, r, has_source_)) specs.push_back(r);
+      if (lean_ok(r)) specs.push_back(r);
     }
   }
   for (const KernelSpec& ks : specs) {
@@ -907,6 +956,7 @@ void Solver::tune_schedules() {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    set_walls(sp, l);
       sp.box = box;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
@@ -963,7 +1013,8 @@ KernelSpec Solver::spec_for_depth(int Kp) const {
 // (0.6775-0.6793 against 0.6776-0.6804 ms/step, gpurun_out/r7y).
 bool Solver::pick_sweep_form() const {
   // (the pair kernel has no heat-source form: a source keeps the lean form)
-  return sweep_form_auto() && !has_source_;
+  // (nor a wall form)
+  return sweep_form_auto() && !has_source_ && !walls_;
 }
 
 bool Solver::sweep_form_auto() const {
@@ -997,7 +1048,7 @@ void Solver::calibrate_remainders() {
     KernelSpec kl;
     kl.kind = kspec2_.kind;
     kl.K = K_ + 1;
-    if (!hip::lean_supported(dt_, kl, has_source_)) return;
+    if (!lean_ok(kl)) return;
   }
   struct Events {  // released on every exit (a refused kernel variant throws)
     Backend* be;
@@ -1020,6 +1071,7 @@ void Solver::calibrate_remainders() {
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
       sp.cu_reserved = be_->reserved_cus();
+      if (Kp > 1) set_walls(sp, l);  // (the single-step kernels take no walls; this one is only timed)
       if (Kp == 1) {
         sp.box = l.owned;
         be_->stencil(dt_, sp, kspec_, kCompute);
@@ -1055,7 +1107,7 @@ void Solver::calibrate_remainders() {
   auto as_run = [&](const KernelSpec& f) {
     if (!rl_forms) return f;
     const KernelSpec r = last_only(f);
-    return hip::lean_supported(dt_, r, has_source_) ? r : f;
+    return lean_ok(r) ? r : f;
   };
   std::vector<Cand> cands{{K_, as_run(kspec2_), "sweep" + std::to_string(K_), kspec2_},
                           {K_ + 1, as_run(spec_for_depth(K_ + 1)), "sweep" + std::to_string(K_ + 1),
@@ -1067,14 +1119,14 @@ void Solver::calibrate_remainders() {
     // (the every-residual form spills: iteration 0's sweep and the replay of
     // one that converged run the default K + 1 shape)
     const KernelSpec t = KernelSpec::parse("tl4:1:4:1:12:0:3:66");
-    if (hip::lean_supported(dt_, t, has_source_))
+    if (lean_ok(t))
       cands.push_back({K_ + 1, t, "sweep" + std::to_string(K_ + 1) + "[" + t.str() + "]", spec_for_depth(K_ + 1)});
     // ... and the same 12 waves with the edge role (spec field 9): the two
     // halo waves evaluate only the stages inside the tile's cone, and with two
     // owned rows each the tile stores 44 of 52 rows
     for (const char* v : {"tl4:1:4:1:12:0:3:66:0:1", "tl4:1:4:1:12:0:3:66:0:3"}) {
       const KernelSpec e = KernelSpec::parse(v);
-      if (hip::lean_supported(dt_, e, has_source_))
+      if (lean_ok(e))
         cands.push_back({K_ + 1, e, "sweep" + std::to_string(K_ + 1) + "[" + e.str() + "]", spec_for_depth(K_ + 1)});
     }
   }
@@ -1084,14 +1136,14 @@ void Solver::calibrate_remainders() {
     cands.push_back({K_, pr, "sweep" + std::to_string(K_) + "[" + pr.resolved(dt_).str() + "]", pair_form()});
     KernelSpec pl = pair_form();  // and the pair form of the long sweep
     pl.K = K_ + 1;
-    if (hip::lean_supported(dt_, pl, has_source_))
+    if (lean_ok(pl))
       cands.push_back({K_ + 1, as_run(pl), "sweep" + std::to_string(K_ + 1) + "[" + pl.resolved(dt_).str() + "]", pl});
   }
   for (int r = 1; r < K_; ++r) {
     if (r == 2 && dt_ == DType::F64 && kspec2_.kind == KernelSpec::TBL && be_->is_gpu()) {
       for (const char* v : {"tl2:1:5:1:16:0:3:2", "tl2:1:3:1:16:0:3:2", "tl2:2:6:1:8:0:3:2"}) {
         const KernelSpec ks = KernelSpec::parse(v);
-        if (hip::lean_supported(dt_, ks, has_source_)) cands.push_back({2, as_run(ks), std::string("sweep2[") + v + "]", ks});
+        if (lean_ok(ks)) cands.push_back({2, as_run(ks), std::string("sweep2[") + v + "]", ks});
       }
       continue;
     }
@@ -1261,6 +1313,7 @@ int Solver::preheat(int sweeps) {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    set_walls(sp, l);
       sp.box = l.tb_interior;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = dstate_;
@@ -1373,6 +1426,9 @@ void Solver::enqueue_iteration(int p, int bi) {
   last_kind_ = 1;
   // [A] interior sweep on the compute stream
   ev_wait(kCompute, EV_CHK + p);  // convergence check of iteration t-2 (flag + slot reset)
+  // insulated walls: T^t's wall planes <- their inward neighbours (a sweep
+  // leaves them stale; the schedule is then the single-stream one below)
+  refresh_walls(bi, kCompute);
   T(0, kCompute);
   if (overlap_) {
     ev_wait(kCompute, EV_BND + (p ^ 1));  // shell of t-1 written (and read) before we overwrite
@@ -1471,6 +1527,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
     sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    set_walls(sp, l);
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1603,7 +1660,8 @@ bool Solver::residual_last_ok() const {
   // fp32 with a heat source: every residual (the source cancels in T'' - T'
   // in exact arithmetic only; the fp32 rounding defect of the monotone check
   //  is not extended to source runs)
-  if (has_source_ && dt_ == DType::F32) return false;
+  // (nor to insulated walls)
+  if ((has_source_ || walls_) && dt_ == DType::F32) return false;
   return cfg_.monotone_check && be_->is_gpu() && tb_ && cfg_.verbose <= 0 && c >= 0.0 && fake_allreduce_us_ <= 0;
 }
 
@@ -1653,6 +1711,7 @@ void Solver::resolve_coarse() {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    set_walls(sp, l);
       sp.box = b;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = rstate_;
@@ -1854,6 +1913,7 @@ void Solver::finalize_converged(int64_t c) {
     for (int j = 1; j <= m; ++j) {
       const int src = (j & 1) ? s.inbuf : nxt(s.inbuf);
       const int dst = (j & 1) ? nxt(s.inbuf) : s.inbuf;
+      refresh_walls(src, kCompute);
       for (auto& l : local_) {
         StencilParams sp;
         sp.in = l.field[src];
@@ -1933,7 +1993,7 @@ int Solver::long_sweeps_for(int64_t n) const {
   KernelSpec ks;
   ks.kind = kspec2_.kind;
   ks.K = K_ + 1;
-  return be_->is_gpu() && !hip::lean_supported(dt_, ks, has_source_) ? 0 : (int)b;
+  return be_->is_gpu() && !lean_ok(ks) ? 0 : (int)b;
 }
 
 bool Solver::graphs_allowed() const {
@@ -2218,6 +2278,14 @@ HostState Solver::state() {
   h.done = hstate_->done;
   h.fault = hstate_->fault;
   return h;
+}
+
+std::vector<double> Solver::residual_history() {
+  const HostState h = state();  // a fresh copy of the device state in hstate_
+  std::vector<double> out;
+  const int64_t cap = hstate_->hist_cap;
+  for (int64_t t = std::max<int64_t>(0, h.iter - cap); t < h.iter && cap > 0; ++t) out.push_back(hstate_->hist[t % cap]);
+  return out;
 }
 
 RunResult Solver::run() {

@@ -83,7 +83,9 @@ class Solver {
   std::string kernel_name() const {
     const std::string one = kspec_.resolved(cfg_.dtype).str();
     if (cond_sweeping()) return spec_for_depth(Kc_).str() + "+" + one;
-    return sweeping() ? kspec2_.resolved(cfg_.dtype).str() + "+" + one : one;
+    KernelSpec k2 = kspec2_;
+    if (walls_ && k2.V == 0) k2.V = 1;  // (the wall forms: one value per lane for fp32 too)
+    return sweeping() ? k2.resolved(cfg_.dtype).str() + "+" + one : one;
   }
 
   // (Re)initialise fields: analytic IC/BC (heat3D.cu:408-453) or restart.
@@ -104,6 +106,10 @@ class Solver {
   void prepare_steps(int64_t n);
   void synchronize();
   HostState state();
+  // the max-norm residuals of the last iterations checked (up to 1024, oldest
+  // first; with the monotone check only the iterations whose residual a sweep
+  // computed)
+  std::vector<double> residual_history();
   int64_t iterations_issued() const { return issued_; }
   // hipGraph launches so far (what actually ran, not the --graph request)
   int64_t graph_launches() const { return graph_launches_; }
@@ -158,6 +164,9 @@ class Solver {
   // K-step sweeps are what run() / step() issue (temporal blocking on, and no
   // conductivity field or Config::cond_sweeps)
   bool sweeps_active() const { return sweeping(); }
+  // ... in the overlapped schedule (interior on the compute stream, deep halo
+  // and boundary pieces on the comm stream; sweep_pieces lists the pieces)
+  bool sweeps_overlapped() const { return sweeping() && tb_overlap_; }
   void set_field_file(const std::string& path);
 
   // Error vs analytic steady state (heat3D.cu:1093-1106, with a true global
@@ -284,6 +293,9 @@ class Solver {
     std::vector<Box> tb_boundary_long;
     int64_t ux[2] = {0, -1};
     int64_t uy[2] = {0, -1}, uz[2] = {0, -1};  // y / z update ranges (deep y / z halos)
+    // insulated walls: local coordinate of the wall-adjacent plane per axis and
+    // side (StencilParams::wall), from the global indices 1 and N - 2
+    int64_t wall[3][2] = {{kNoWall, kNoWall}, {kNoWall, kNoWall}, {kNoWall, kNoWall}};
   };
 
   void setup_faces();
@@ -300,9 +312,24 @@ class Solver {
   bool has_cond_ = false;
   // K-step sweeps run (temporal blocking on, and no conductivity field or the
   // tv sweeps asked for)
-  bool sweeping() const { return tb_ && (!has_cond_ || cond_sweeping()); }
+  bool sweeping() const { return tb_ && (!has_cond_ || cond_sweeping()) && !walls_single(); }
   // ... of the tv family, with the conductivity field (--conductivity-sweeps)
-  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2; }
+  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2 && !walls_; }
+  // Insulated walls (Config::insulated).  Sweeps run the wall forms of the
+  // lean kernel (StencilParams::wall: the substitution happens in the kernel,
+  // at every stage).  Single steps run the kernels as they are on wall planes
+  // refreshed from their inward neighbours (refresh_walls), which gives the
+  // same bits.  With a source or a conductivity as well there is no sweep
+  // form: every iteration is such a single step (walls_single).
+  unsigned walls_ = 0;
+  bool walls_single() const { return walls_ && (has_source_ || has_cond_); }
+  void set_walls(StencilParams& sp, const Local& l) const;
+  // wall planes of buffer b <- their inward neighbours, axis order x, y, z,
+  // over the whole local extent of the other axes (ghosts included); vertices
+  // on a Dirichlet face are left alone
+  void refresh_walls(int b, StreamId s);
+  // is the lean variant built in the form this run needs (source / walls)?
+  bool lean_ok(const KernelSpec& ks) const;
   // steps per sweep of the schedule: K_, or the tv sweeps' depth Kc_ <= K_ (a
   // sweep shallower than the ghost depth K_ is what a partial sweep is)
   int sweep_depth() const { return cond_sweeping() ? Kc_ : K_; }

@@ -22,6 +22,8 @@
 namespace heat3d {
 std::vector<double> Solver::local_field(int idx, bool with_ghosts) {
   be_->sync_all();
+  refresh_walls(cur(), kCompute);  // what the host sees of an insulated wall: copies of the inward neighbours
+  be_->sync(kCompute);
   auto& l = local_.at(idx);
   Box b;
   for (int a = 0; a < 3; ++a) {
@@ -91,6 +93,8 @@ static void stream_box_out(Backend& be, DType dt, std::size_t esize, const void*
 
 bool Solver::gather_global(std::vector<double>* out) {
   be_->sync_all();
+  refresh_walls(cur(), kCompute);
+  be_->sync(kCompute);
   const int P = comm_->size();
   const bool root = is_root();
   const int p = cur();
@@ -221,6 +225,8 @@ void Solver::write_tecplot(const std::string& path, const std::string& layout_re
 // more than one staging chunk, whatever the grid size.
 void Solver::write_tecplot_zones(const std::string& path) {
   be_->sync_all();
+  refresh_walls(cur(), kCompute);
+  be_->sync(kCompute);
   const int P = comm_->size();
   HEAT3D_CHECK(P < 100000, "rank column is %5d");
   const bool rank_column = P > 1;
@@ -343,6 +349,8 @@ unsigned long long Solver::allreduce_sum_u64(unsigned long long v) {
 // restart checks the file size and the checksum.
 void Solver::save_checkpoint(const std::string& dir) {
   be_->sync_all();
+  refresh_walls(cur(), kCompute);
+  be_->sync(kCompute);
   HostState hs = state();
   const int p = cur();
   const int64_t* N = dec_.N;
@@ -411,6 +419,7 @@ void Solver::save_checkpoint(const std::string& dir) {
     j.set_raw("has_source", has_source_ ? "true" : "false");
     // nor the conductivity field
     j.set_raw("has_conductivity", has_cond_ ? "true" : "false");
+    j.set("insulated", insulated_str(walls_));
     io::write_file_atomic(dir + "/meta.json", j.dump() + "\n");
     // older field files, and the temp files of saves that a crash
     // interrupted (a full-grid field.<iter>.raw.tmp each)
@@ -441,6 +450,12 @@ void Solver::load_checkpoint(const std::string& dir) {
   HEAT3D_CHECK(!(meta.count("has_conductivity") && meta["has_conductivity"] == "true") || has_cond_,
                "checkpoint " << dir << " was written with a conductivity field, which is not stored in it: set it "
                                        "again (set_conductivity / --conductivity) before loading it");
+  // (checkpoints older than the insulated walls have no such key: all Dirichlet)
+  {
+    const std::string was = meta.count("insulated") ? meta["insulated"] : std::string("none");
+    HEAT3D_CHECK(was == insulated_str(walls_), "checkpoint " << dir << " was written with --insulated " << was
+                                                               << ", this run has --insulated " << insulated_str(walls_));
+  }
   const int64_t it = std::atoll(meta["iteration"].c_str());
   const double norm = std::atof(meta["norm"].c_str());
   const int64_t* N = dec_.N;
@@ -730,6 +745,9 @@ void Solver::set_field_rows(const GlobalRows& rows) {
     void* bufs[3] = {l.field[0], l.field[1], l.field[2]};
     scatter_global(rows, 1.0, l, bufs, nbuf_);
   }
+  // values given on insulated faces are ignored
+  for (int b = 0; b < nbuf_; ++b) refresh_walls(b, kCompute);
+  be_->sync(kCompute);
   reset_state(false);
 }
 

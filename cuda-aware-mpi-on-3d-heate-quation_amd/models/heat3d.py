@@ -102,6 +102,25 @@ class HeatEquation3D:
         p = r / r[-1]
         return np.broadcast_to(p[None, :, None], self.n).copy()
 
+    def neumann_mode(self, axis: int, m: int) -> Tuple[np.ndarray, float]:
+        """Discrete eigenmode of the update between two insulated walls of
+        ``axis``: cos(pi m (j - 1/2) / M) at the interior vertices j = 1..M,
+        M = N - 2, constant along the other axes (global array; the wall
+        vertices hold copies of their inward neighbours).  With every face
+        insulated one step multiplies it by the returned factor
+        g = 1 - 4 D_axis sin^2(pi m / (2 M))."""
+        N = self.n[axis]
+        M = N - 2
+        j = np.arange(1, M + 1, dtype=np.float64)
+        v = np.empty(N, dtype=np.float64)
+        v[1:-1] = np.cos(np.pi * m * (j - 0.5) / M)
+        v[0], v[-1] = v[1], v[-2]
+        shape = [1, 1, 1]
+        shape[axis] = N
+        T = np.broadcast_to(v.reshape(shape), self.n).copy()
+        g = 1.0 - 4.0 * self.D[axis] * np.sin(np.pi * m / (2.0 * M)) ** 2
+        return T, float(g)
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -128,7 +147,8 @@ class HeatSolver:
                  kernel: str = "auto", graph: bool = True, overlap: bool = True,
                  check_every: int = 64, graph_chunk: int = 0, device: Optional[int] = None,
                  threads: int = 0, extra_args: Sequence[str] = (), group=None,
-                 phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False):
+                 phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False,
+                 insulated=None):
         ext = native()
         self.model = HeatEquation3D(tuple(int(v) for v in n))  # type: ignore[arg-type]
         args: List[str] = [str(int(v)) for v in n] + [str(int(iter_max)), _fmt(eps)]
@@ -149,6 +169,10 @@ class HeatSolver:
         if conductivity_sweeps:
             # with a conductivity field: K-step sweeps of the tv kernels instead of single steps
             args.append("--conductivity-sweeps")
+        if insulated:
+            # zero-flux walls: names of x-, x+, y-, y+, z-, z+ (a sequence or a comma list) or "all";
+            # the native parser validates them (UsageError)
+            args += ["--insulated", insulated if isinstance(insulated, str) else ",".join(str(f) for f in insulated)]
         args += list(extra_args)
         self.args = args
 

@@ -94,12 +94,48 @@ def _cond_ptr(src: PaddedField, conductivity: Optional[PaddedField]) -> int:
     return conductivity.data_ptr()
 
 
+FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
+
+
+def insulated_mask(insulated) -> int:
+    """Face mask (bit 2 * axis + side) of ``insulated``: None, an int mask,
+    ``"all"``, a comma list or a sequence of the names x-, x+, y-, y+, z-, z+.
+    An unknown name is the native UsageError."""
+    if insulated is None:
+        return 0
+    if isinstance(insulated, int):
+        if not 0 <= insulated < 64:
+            raise ValueError(f"insulated mask {insulated} outside [0, 64)")
+        return insulated
+    text = insulated if isinstance(insulated, str) else ",".join(str(f) for f in insulated)
+    return native().parse_insulated(text) if text else 0
+
+
+def wall_coords(mask: int, n: Sequence[int], gstart: Sequence[int] = (1, 1, 1),
+                N: Optional[Sequence[int]] = None) -> list:
+    """``walls`` argument of the kernels: per face the local coordinate of the
+    updated plane next to the insulated wall (global index 1 or N - 2), NO_WALL
+    for a Dirichlet face.  Default: the block is the whole interior of its grid."""
+    none = native().NO_WALL
+    out = []
+    for a in range(3):
+        Na = N[a] if N is not None else n[a] + 2
+        out.append(1 - gstart[a] if (mask >> (2 * a)) & 1 else none)
+        out.append(Na - 2 - gstart[a] if (mask >> (2 * a + 1)) & 1 else none)
+    return out
+
+
 def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
               box: Optional[Sequence[int]] = None, kernel: str = "auto",
               state: Optional[torch.Tensor] = None, slot: int = 0,
               source: Optional[PaddedField] = None,
-              conductivity: Optional[PaddedField] = None) -> None:
+              conductivity: Optional[PaddedField] = None,
+              walls: Optional[Sequence[int]] = None) -> None:
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
+
+    ``walls``: insulated walls as ``wall_coords`` gives them (CPU tensors only,
+    without source / conductivity: the single-step gfx950 kernels run on wall
+    planes copied from their inward neighbours instead).
 
     ``source``: optional field S = dtype(dt * q) in the same layout, added to
     every updated point (kernels.hpp ftcs_update_src).
@@ -129,10 +165,13 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
     qptr = _source_ptr(src, source)
     cptr = _cond_ptr(src, conductivity)
     if src.device.type == "cuda":
+        if walls is not None:
+            raise ValueError("the single-step gfx950 kernels take no walls (copy the wall planes first)")
         ext.hip.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot,
                         kernel, _stream_ptr(src.flat), qptr, cptr)
     else:
-        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr)
+        w = list(walls) if walls is not None else [ext.NO_WALL] * 6
+        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr, w)
 
 
 def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: str = "auto",
@@ -191,13 +230,16 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
 
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
            kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0,
-           source: Optional[PaddedField] = None, conductivity: Optional[PaddedField] = None) -> None:
+           source: Optional[PaddedField] = None, conductivity: Optional[PaddedField] = None,
+           walls: Optional[Sequence[int]] = None) -> None:
     """K-step sweep with deep ghosts on every axis (the block-decomposition
     schedule): ``u`` = (ux0, ux1, uy0, uy1, uz0, uz1) are the update ranges of
     the intermediate steps.  GPU tensors run the lean kernel, CPU tensors the
     K-single-steps definition.  ``source``: optional heat-source field S in the
     same layout (deep ghosts included), added at every step.  ``conductivity``:
-    as in ``sweep`` (GPU: ``tv2`` / ``tv3``)."""
+    as in ``sweep`` (GPU: ``tv2`` / ``tv3``).  ``walls``: insulated walls as
+    ``wall_coords`` gives them; GPU tensors run the wall form of the lean
+    kernel (stencil_tbl_wall.hip; a spec without one is a RuntimeError)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -209,10 +251,11 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
             list(D), sptr, slot, kernel)
     qptr = _source_ptr(src, source)
     cptr = _cond_ptr(src, conductivity)
+    w = list(walls) if walls is not None else [native().NO_WALL] * 6
     if src.device.type == "cuda":
-        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr)
+        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr, w)
     else:
-        native().cpu.stencil_sweep3(*args, qptr, cptr)
+        native().cpu.stencil_sweep3(*args, qptr, cptr, w)
 
 
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
@@ -234,8 +277,13 @@ def unpack_box(f: PaddedField, box: Sequence[int], buf: torch.Tensor) -> None:
 
 
 def ftcs_reference(T: torch.Tensor, D: Sequence[float], src: Optional[torch.Tensor] = None,
-                   cond: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, float]:
+                   cond: Optional[torch.Tensor] = None, insulated=None) -> Tuple[torch.Tensor, float]:
     """Plain-PyTorch FTCS on a ghosted block; returns (new interior, max |dT|).
+
+    ``insulated``: faces of the block that are zero-flux walls (``insulated_mask``
+    forms; the block is the whole grid).  The ghost plane of such a face is
+    replaced by a copy of the first interior plane before the update, so the
+    neighbour across the wall is the centre value.
 
     ``cond``: optional ghosted block (shape of ``T``) of Ch = dtype(0.5 * c),
     c the relative conductivity: the update of kernels.hpp ftcs_update_var.
@@ -252,6 +300,14 @@ def ftcs_reference(T: torch.Tensor, D: Sequence[float], src: Optional[torch.Tens
         return (F[1:-1, 1:-1, 1:-1], F[:-2, 1:-1, 1:-1], F[2:, 1:-1, 1:-1], F[1:-1, :-2, 1:-1], F[1:-1, 2:, 1:-1],
                 F[1:-1, 1:-1, :-2], F[1:-1, 1:-1, 2:])
 
+    mask = insulated_mask(insulated)
+    if mask:
+        T = T.clone()
+        for a in range(3):
+            if (mask >> (2 * a)) & 1:
+                T.select(a, 0).copy_(T.select(a, 1).clone())
+            if (mask >> (2 * a + 1)) & 1:
+                T.select(a, T.shape[a] - 1).copy_(T.select(a, T.shape[a] - 2).clone())
     c = T[1:-1, 1:-1, 1:-1]
     if cond is not None:
         if cond.shape != T.shape or cond.dtype != T.dtype:
