@@ -147,6 +147,8 @@ static int drive(const Config& cfg, Solver& solver) {
     j.set("kernel", solver.kernel_name());
     j.set_bool("conductivity_sweeps", cfg.cond_sweeps);
     j.set("insulated", insulated_str(cfg.insulated));
+    j.set("convective", convective_str(cfg.convective));
+    j.set("ambient", cfg.ambient);
     j.set("eps", cfg.eps);
     j.set("iter_max", (int64_t)cfg.iter_max);
     j.set_bool("converged", r.converged);

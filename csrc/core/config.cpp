@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <iomanip>
@@ -75,6 +76,69 @@ std::string insulated_str(unsigned mask) {
   return out.empty() ? "none" : out;
 }
 
+static std::string g17(double v) {
+  char buf[40];
+  std::snprintf(buf, sizeof(buf), "%.17g", v);
+  // the shortest of %.15g .. %.17g that reads back as v
+  for (int prec = 15; prec < 17; ++prec) {
+    char b2[40];
+    std::snprintf(b2, sizeof(b2), "%.*g", prec, v);
+    if (std::strtod(b2, nullptr) == v) return b2;
+  }
+  return buf;
+}
+
+ConvectiveFaces parse_convective(const std::string& s) {
+  ConvectiveFaces out;
+  out.fill(-1.0);
+  if (s == "none") return out;
+  const std::string want = " (want a list of FACE=BETA with FACE one of x-,x+,y-,y+,z-,z+ or all, 0 <= BETA <= 1)";
+  if (s.empty() || s.back() == ',') throw UsageError("bad --convective '" + s + "'" + want);
+  std::stringstream ss(s);
+  std::string item;
+  while (std::getline(ss, item, ',')) {
+    const auto eq = item.find('=');
+    if (eq == std::string::npos) throw UsageError("bad --convective entry '" + item + "'" + want);
+    const std::string name = item.substr(0, eq), val = item.substr(eq + 1);
+    double beta = 0;
+    try {
+      size_t pos = 0;
+      beta = std::stod(val, &pos);
+      if (pos != val.size()) throw std::invalid_argument(val);
+    } catch (const std::exception&) {
+      throw UsageError("bad --convective coefficient '" + val + "'" + want);
+    }
+    if (!std::isfinite(beta) || beta < 0.0 || beta > 1.0)
+      throw UsageError("--convective coefficient " + val + " of face " + name + " outside [0, 1]" + want);
+    if (name == "all") {
+      out.fill(beta);
+      continue;
+    }
+    int f = -1;
+    for (int i = 0; i < 6; ++i)
+      if (name == kFaceNames[i]) f = i;
+    if (f < 0) throw UsageError("bad --convective face '" + name + "'" + want);
+    out[f] = beta;
+  }
+  return out;
+}
+
+unsigned convective_mask(const ConvectiveFaces& c) {
+  unsigned m = 0;
+  for (int i = 0; i < 6; ++i)
+    if (c[i] >= 0.0) m |= 1u << i;
+  return m;
+}
+
+std::string convective_str(const ConvectiveFaces& c) {
+  std::string out;
+  for (int i = 0; i < 6; ++i)
+    if (c[i] >= 0.0) out += (out.empty() ? "" : ",") + std::string(kFaceNames[i]) + "=" + g17(c[i]);
+  return out.empty() ? "none" : out;
+}
+
+std::string ambient_str(double t) { return g17(t); }
+
 std::array<int, 3> parse_decomp(const std::string& s) {
   std::array<int, 3> d = {0, 0, 0};
   int idx = 0;
@@ -135,6 +199,11 @@ std::string Config::usage() {
      << "                            as --source; iterations then run as single steps (no K-step sweeps)\n"
      << "  --insulated FACES         zero-flux (adiabatic) walls: a list of x-,x+,y-,y+,z-,z+ or all; the other\n"
      << "                            faces stay Dirichlet (not with --compat)\n"
+     << "  --convective FACE=BETA,.. convective (Robin) walls, -k dT/dn = h (T - T_inf): a list such as y-=0.5,x+=0.25\n"
+     << "                            or all=0.5; the neighbour across such a wall is T + BETA (T_inf - T), 0 <= BETA <= 1\n"
+     << "                            (BETA = 2 Bi / (2 + Bi), Bi = h * spacing / k; 0 is an insulated wall); a face is\n"
+     << "                            Dirichlet, insulated or convective (not with --compat)\n"
+     << "  --ambient T               the ambient temperature T_inf of the convective walls (default 0)\n"
      << "  --conductivity-sweeps     with a conductivity field: K-step sweeps of the tv kernels (tv2 / tv3,\n"
      << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
@@ -285,6 +354,11 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
     else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
+    else if (key == "--convective") c.convective = parse_convective(get("--convective"));
+    else if (key == "--ambient") {
+      c.ambient = to_f64(get("--ambient"), "--ambient");
+      if (!std::isfinite(c.ambient)) throw UsageError("--ambient must be finite");
+    }
     else if (key == "--json-out") c.json_out = get("--json-out");
     else if (key == "--verbose") c.verbose = (int)to_i64(get("--verbose"), "--verbose");
     else if (key == "--progress") c.progress_s = to_f64(get("--progress"), "--progress");
@@ -405,6 +479,12 @@ Config Config::parse(int argc, const char* const* argv) {
     throw UsageError("--conductivity is not part of --compat (the reference's uniform material)");
   if (c.insulated && (c.compat || c.scheme == "reference"))
     throw UsageError("--insulated is not part of --compat / --scheme reference (the reference's Dirichlet walls)");
+  if (convective_mask(c.convective) && (c.compat || c.scheme == "reference"))
+    throw UsageError("--convective is not part of --compat / --scheme reference (the reference's Dirichlet walls)");
+  if (convective_mask(c.convective) & c.insulated)
+    throw UsageError("a face is either insulated or convective: --insulated " + insulated_str(c.insulated) +
+                     " and --convective " + convective_str(c.convective) + " share " +
+                     insulated_str(convective_mask(c.convective) & c.insulated));
   if (c.cond_sweeps && c.compat)
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
   return c;
@@ -419,7 +499,12 @@ std::string Config::echo_banner() const {
   os << "number of cells in y:     " << n[1] << "\n";
   os << "number of cells in z:     " << n[2] << "\n";
   os << "max number of iterations: " << iter_max << "\n";
-  os << "convergence threshold:    " << eps << "\n\n";
+  os << "convergence threshold:    " << eps << "\n";
+  if (convective_mask(convective)) {
+    os << "convective walls:         " << convective_str(convective) << "\n";
+    os << "ambient temperature:      " << ambient_str(ambient) << "\n";
+  }
+  os << "\n";
   return os.str();
 }
 

@@ -74,6 +74,11 @@ struct Config {
   // --insulated: faces of the global grid that are zero-flux walls instead of
   // Dirichlet ones, bit 2 * axis + side (x-, x+, y-, y+, z-, z+; parse_insulated)
   unsigned insulated = 0;
+  // --convective: per face (same order) the coefficient beta in [0, 1] of a
+  // convective (Robin) wall, negative where the face is not convective;
+  // --ambient: the ambient temperature T_inf of those walls
+  std::array<double, 6> convective = {-1, -1, -1, -1, -1, -1};
+  double ambient = 0;
   std::string json_out;
   int verbose = 0;
   double progress_s = 0;          // run(): stderr heartbeat period (0 = off)
@@ -142,5 +147,12 @@ std::array<int, 3> parse_decomp(const std::string& s);
 // "x-,x+,z-" | "all" | "none" -> face mask (bit 2 * axis + side); unknown names throw UsageError
 unsigned parse_insulated(const std::string& s);
 std::string insulated_str(unsigned mask);  // the canonical list ("none" for 0)
+// "y-=0.5,x+=0.25" | "all=0.5" | "none" -> coefficient per face, -1 where not convective;
+// unknown faces and coefficients outside [0, 1] or not finite throw UsageError
+using ConvectiveFaces = std::array<double, 6>;
+ConvectiveFaces parse_convective(const std::string& s);
+unsigned convective_mask(const ConvectiveFaces& c);    // faces with a coefficient
+std::string convective_str(const ConvectiveFaces& c);  // the canonical list, values round-trip ("none")
+std::string ambient_str(double t);
 
 }  // namespace heat3d

@@ -81,6 +81,39 @@ double ftcs_row_wall_f32(const float* in, float* out, int64_t n, int64_t oxm, in
   return row_wall<float>(in, out, n, oxm, oxp, oym, oyp, kzm, kzp, Dx, Dy, Dz);
 }
 
+// convective walls: as row_wall, with the ghost convective_ghost(T, beta, tinf)
+// in place of T (beta: x-, x+, y-, y+, z-, z+; 0 on an insulated face)
+template <typename Real>
+static inline double row_conv(const Real* __restrict in, Real* __restrict out, int64_t n, int64_t oxm, int64_t oxp,
+                              int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf, Real Dx,
+                              Real Dy, Real Dz) {
+  double lres = 0.0;
+  bool nan = false;
+  const Real bxm = beta[0], bxp = beta[1], bym = beta[2], byp = beta[3], bzm = beta[4], bzp = beta[5];
+  for (int64_t k = 0; k < n; ++k) {
+    const Real T = in[k];
+    const Real d = tinf - T;
+    const Real xm = oxm ? in[k + oxm] : h3d_fma(bxm, d, T), xp = oxp ? in[k + oxp] : h3d_fma(bxp, d, T);
+    const Real ym = oym ? in[k + oym] : h3d_fma(bym, d, T), yp = oyp ? in[k + oyp] : h3d_fma(byp, d, T);
+    const Real zm = k == kzm ? h3d_fma(bzm, d, T) : in[k - 1], zp = k == kzp ? h3d_fma(bzp, d, T) : in[k + 1];
+    const Real nv = ftcs_update<Real>(T, xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);
+    out[k] = nv;
+    const double r = resid_abs(nv, T);
+    nan |= r != r;
+    lres = r > lres ? r : lres;
+  }
+  return nan ? std::nan("") : lres;
+}
+
+double ftcs_row_conv_f64(const double* in, double* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym, int64_t oyp,
+                         int64_t kzm, int64_t kzp, const double* beta, double tinf, double Dx, double Dy, double Dz) {
+  return row_conv<double>(in, out, n, oxm, oxp, oym, oyp, kzm, kzp, beta, tinf, Dx, Dy, Dz);
+}
+double ftcs_row_conv_f32(const float* in, float* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym, int64_t oyp,
+                         int64_t kzm, int64_t kzp, const float* beta, float tinf, float Dx, float Dy, float Dz) {
+  return row_conv<float>(in, out, n, oxm, oxp, oym, oyp, kzm, kzp, beta, tinf, Dx, Dy, Dz);
+}
+
 double ftcs_row_f64(const double* in, double* out, int64_t n, int64_t sx, int64_t sy, double Dx, double Dy,
                     double Dz) {
   return row<double, false>(in, out, nullptr, n, sx, sy, Dx, Dy, Dz);
@@ -117,10 +150,12 @@ const RowKernels& cpu_row_kernels() {
     if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2"))
       return RowKernels{rows_fma::ftcs_row_f64, rows_fma::ftcs_row_f32, "x86-64+fma+avx2", rows_fma::ftcs_row_src_f64,
                         rows_fma::ftcs_row_src_f32, rows_fma::ftcs_row_var_f64, rows_fma::ftcs_row_var_f32,
-                        rows_fma::ftcs_row_wall_f64, rows_fma::ftcs_row_wall_f32};
+                        rows_fma::ftcs_row_wall_f64, rows_fma::ftcs_row_wall_f32, rows_fma::ftcs_row_conv_f64,
+                        rows_fma::ftcs_row_conv_f32};
     return RowKernels{rows_generic::ftcs_row_f64, rows_generic::ftcs_row_f32, "x86-64 (libm fma)",
                       rows_generic::ftcs_row_src_f64, rows_generic::ftcs_row_src_f32, rows_generic::ftcs_row_var_f64,
-                      rows_generic::ftcs_row_var_f32, rows_generic::ftcs_row_wall_f64, rows_generic::ftcs_row_wall_f32};
+                      rows_generic::ftcs_row_var_f32, rows_generic::ftcs_row_wall_f64, rows_generic::ftcs_row_wall_f32,
+                      rows_generic::ftcs_row_conv_f64, rows_generic::ftcs_row_conv_f32};
   }();
   return k;
 }

@@ -38,6 +38,14 @@ template <typename Real>
 using FtcsRowWallFn = double (*)(const Real* in, Real* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym,
                                  int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz);
 
+// convective walls (StencilParams::wall_beta): as FtcsRowWallFn, with the
+// coefficients of the six faces (x-, x+, y-, y+, z-, z+; 0 on an insulated one)
+// and the ambient temperature
+template <typename Real>
+using FtcsRowConvFn = double (*)(const Real* in, Real* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym,
+                                 int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf, Real Dx, Real Dy,
+                                 Real Dz);
+
 struct RowKernels {
   FtcsRowFn<double> f64;
   FtcsRowFn<float> f32;
@@ -48,6 +56,8 @@ struct RowKernels {
   FtcsRowVarFn<float> var_f32;
   FtcsRowWallFn<double> wall_f64;
   FtcsRowWallFn<float> wall_f32;
+  FtcsRowConvFn<double> conv_f64;
+  FtcsRowConvFn<float> conv_f32;
 };
 
 const RowKernels& cpu_row_kernels();
@@ -65,6 +75,10 @@ double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int6
                          double, double);
 double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
                          float, float);
+double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                         const double*, double, double, double, double);
+double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                         const float*, float, float, float, float);
 }  // namespace rows_generic
 namespace rows_fma {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
@@ -79,6 +93,10 @@ double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int6
                          double, double);
 double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
                          float, float);
+double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                         const double*, double, double, double, double);
+double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                         const float*, float, float, float, float);
 }  // namespace rows_fma
 
 }  // namespace cpu

@@ -108,6 +108,23 @@ struct StencilParams {
       if (wall[a][0] != kNoWall || wall[a][1] != kNoWall) return true;
     return false;
   }
+  // Convective (Robin) walls, -k dT/dn = h (T - T_inf): a face with a wall
+  // coordinate above and wall_beta[a][e] >= 0 is convective with that
+  // coefficient (0 <= beta <= 1; negative: the face is insulated or has no
+  // wall).  The neighbour across such a wall is replaced by
+  // convective_ghost(c, Real(beta), Real(ambient)) instead of the centre value
+  // c; beta = 0 gives c, the insulated wall.  Once any face is convective the
+  // insulated faces of the same call are evaluated as coefficient 0 (every
+  // backend alike).  Honoured where `wall` is: cpu::stencil / stencil_multi and
+  // the convective forms of the lean sweep (stencil_tbl_conv.hip).
+  double wall_beta[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
+  double ambient = 0;
+  bool has_convective() const {
+    for (int a = 0; a < 3; ++a)
+      for (int e = 0; e < 2; ++e)
+        if (wall[a][e] != kNoWall && wall_beta[a][e] >= 0) return true;
+    return false;
+  }
 };
 
 struct InitParams {
@@ -174,9 +191,17 @@ int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, 
 // Is the lean kernel variant that k resolves to for dtype t instantiated?
 // with_source: its heat-source form (StencilParams::src != nullptr)
 // with_walls: its insulated-wall form (StencilParams::has_walls; no source form)
-bool lean_supported(DType t, const KernelSpec& k, bool with_source = false, bool with_walls = false);
+// with_convective: its convective-wall form (StencilParams::has_convective; implies walls)
+bool lean_supported(DType t, const KernelSpec& k, bool with_source = false, bool with_walls = false,
+                    bool with_convective = false);
 // the wall forms' dispatch (stencil_tbl_wall.hip); p == nullptr: only report
 bool lean_wall_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
+// the convective forms' (stencil_tbl_conv.hip)
+bool lean_conv_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
+// Convective walls on single steps: dst box (one wall plane) <- the ghost value
+// convective_ghost of the src box (the first interior plane), same field
+void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,
+                        double ambient, void* stream);
 // K-step sweep with a conductivity field (stencil_tbv.hip; spec tvK): needs
 // p.cond, honours p.src; no fused check, no schedule tuning
 void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
@@ -247,6 +272,8 @@ void pack_box(DType t, const void* f, const Layout& L, const Box& b, void* buf);
 void unpack_box(DType t, void* f, const Layout& L, const Box& b, const void* buf);
 void copy_box(DType t, const void* src, const Layout& Ls, const Box& bs, void* dst,
               const Layout& Ld, const Box& bd);
+void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,
+                        double ambient);
 void check_convergence(DeviceState* s, int slot);
 void error_accumulate(DType t, const void* f, const Layout& L, const Box& box,
                       const int64_t gstart[3], double hy, DeviceState* s);
@@ -274,6 +301,15 @@ H3D_HD inline Real ftcs_update(Real c, Real xm, Real xp, Real ym, Real yp, Real 
   const Real ay = h3d_fma(Real(-2), c, yp) + ym;
   const Real az = h3d_fma(Real(-2), c, zp) + zm;
   return h3d_fma(Dz, az, h3d_fma(Dy, ay, h3d_fma(Dx, ax, c)));
+}
+
+// The value a convective (Robin) wall presents to the update of its first
+// interior point c: the ghost T_0 = T_1 + beta (T_inf - T_1), one subtraction
+// and one fused multiply-add.  beta = 0 gives c (the insulated wall's mirror
+// ghost), beta = 1 the ambient up to rounding.
+template <typename Real>
+H3D_HD inline Real convective_ghost(Real c, Real beta, Real tinf) {
+  return h3d_fma(beta, tinf - c, c);
 }
 
 // FTCS update with a volumetric heat source, T_t = alpha lap(T) + q:

@@ -86,10 +86,20 @@ static void stencil_t(const StencilParams& p) {
     if constexpr (sizeof(Real) == 8) return cpu_row_kernels().wall_f64;
     else return cpu_row_kernels().wall_f32;
   }();
+  const auto rowconv = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().conv_f64;
+    else return cpu_row_kernels().conv_f32;
+  }();
+  // convective walls (StencilParams::wall_beta): the coefficients in the
+  // field's dtype, 0 on the insulated faces of the same call
+  const bool conv = p.has_convective();
+  Real beta[6];
+  for (int f = 0; f < 6; ++f) beta[f] = static_cast<Real>(p.wall_beta[f / 2][f % 2] > 0 ? p.wall_beta[f / 2][f % 2] : 0);
+  const Real tinf = static_cast<Real>(p.ambient);
   // insulated walls (StencilParams::wall): the uniform update only
   const bool walls = p.has_walls();
   HEAT3D_CHECK(!walls || (!p.src && !p.cond),
-               "cpu::stencil: insulated walls with a source or a conductivity run as single steps on copied wall "
+               "cpu::stencil: insulated / convective walls with a source or a conductivity run as single steps on copied wall "
                "planes, not through StencilParams::wall");
   const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
   const Real* __restrict cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
@@ -100,6 +110,9 @@ static void stencil_t(const StencilParams& p) {
       const int64_t c = L.index(i, j, b.lo[2]);
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
       const double lres = nk <= 0 ? 0.0
+                          : conv  ? rowconv(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
+                                            j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
+                                            p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], beta, tinf, Dx, Dy, Dz)
                           : walls ? rowwall(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
                                             j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
                                             p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], Dx, Dy, Dz)
@@ -199,6 +212,26 @@ void copy_box(DType t, const void* src, const Layout& Ls, const Box& bs, void* d
     copy_t(static_cast<const double*>(src), Ls, bs, static_cast<double*>(dst), Ld, bd);
   else
     copy_t(static_cast<const float*>(src), Ls, bs, static_cast<float*>(dst), Ld, bd);
+}
+
+template <typename Real>
+static void refresh_conv_t(Real* f, const Layout& L, const Box& bs, const Box& bd, Real beta, Real tinf) {
+  const int64_t ex = bs.extent(0), ey = bs.extent(1), ez = bs.extent(2);
+#pragma omp parallel for collapse(2) schedule(static) if (omp_worth(bs.volume()))
+  for (int64_t i = 0; i < ex; ++i)
+    for (int64_t j = 0; j < ey; ++j) {
+      const Real* s = f + L.index(bs.lo[0] + i, bs.lo[1] + j, bs.lo[2]);
+      Real* d = f + L.index(bd.lo[0] + i, bd.lo[1] + j, bd.lo[2]);
+      for (int64_t k = 0; k < ez; ++k) d[k] = convective_ghost<Real>(s[k], beta, tinf);
+    }
+}
+
+void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta, double ambient) {
+  HEAT3D_CHECK(bs.extent(0) == bd.extent(0) && bs.extent(1) == bd.extent(1) && bs.extent(2) == bd.extent(2),
+               "refresh_convective extent mismatch " << bs.str() << " vs " << bd.str());
+  if (bs.empty()) return;
+  if (t == DType::F64) refresh_conv_t(static_cast<double*>(f), L, bs, bd, beta, ambient);
+  else refresh_conv_t(static_cast<float*>(f), L, bs, bd, static_cast<float>(beta), static_cast<float>(ambient));
 }
 
 void check_convergence(DeviceState* s, int slot) {

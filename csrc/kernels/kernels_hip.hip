@@ -700,6 +700,47 @@ void copy_box(DType t, const void* src, const Layout& Ls, const Box& bs, void* d
   box_copy<2>(t, src, Ls, bs, dst, Ld, bd, S(stream));
 }
 
+// ---- convective wall planes (single steps: Solver::refresh_walls) --------------
+// dst box <- convective_ghost of the src box of the same field, the grid of
+// box_copy_kernel (256 threads: tz z points of 256 / tz rows; z = planes)
+template <typename Real>
+__global__ __launch_bounds__(256) void refresh_convective_kernel(Real* __restrict__ f, Layout L, Box bs, Box bd,
+                                                                 Real beta, Real tinf, int tz_log2) {
+  const int64_t ez = bs.extent(2), ey = bs.extent(1);
+  const int tz = 1 << tz_log2;
+  const int64_t kz = (int64_t)blockIdx.x * tz + (threadIdx.x & (tz - 1));
+  const int64_t j = (int64_t)blockIdx.y * (256 >> tz_log2) + (threadIdx.x >> tz_log2), i = blockIdx.z;
+  if (kz >= ez || j >= ey) return;
+  const Real c = f[L.index(bs.lo[0] + i, bs.lo[1] + j, bs.lo[2] + kz)];
+  f[L.index(bd.lo[0] + i, bd.lo[1] + j, bd.lo[2] + kz)] = convective_ghost<Real>(c, beta, tinf);
+}
+
+void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,
+                        double ambient, void* stream) {
+  HEAT3D_CHECK(bs.extent(0) == bd.extent(0) && bs.extent(1) == bd.extent(1) && bs.extent(2) == bd.extent(2),
+               "refresh_convective extent mismatch " << bs.str() << " vs " << bd.str());
+  if (bs.empty()) return;
+  // both boxes inside the field's allocation (the kernel checks the box only)
+  for (int a = 0; a < 3; ++a) {
+    const int64_t ga = a == 0 ? L.gx : a == 1 ? L.gy : L.gz;
+    HEAT3D_CHECK(bs.lo[a] >= -ga && bs.hi[a] <= L.n[a] + ga && bd.lo[a] >= -ga && bd.hi[a] <= L.n[a] + ga,
+                 "refresh_convective: box " << bs.str() << " -> " << bd.str() << " outside the ghosted layout");
+  }
+  int lg = 0;
+  while (lg < 8 && (int64_t(1) << lg) < bs.extent(2)) ++lg;
+  const int64_t rows = 256 >> lg;
+  HEAT3D_CHECK((bs.extent(1) + rows - 1) / rows < 65536 && bs.extent(0) < 65536, "box too large for refresh grid");
+  dim3 grid((unsigned)((bs.extent(2) + (1 << lg) - 1) >> lg), (unsigned)((bs.extent(1) + rows - 1) / rows),
+            (unsigned)bs.extent(0));
+  if (t == DType::F64)
+    hipLaunchKernelGGL((refresh_convective_kernel<double>), grid, dim3(256), 0, S(stream), static_cast<double*>(f), L,
+                       bs, bd, beta, ambient, lg);
+  else
+    hipLaunchKernelGGL((refresh_convective_kernel<float>), grid, dim3(256), 0, S(stream), static_cast<float*>(f), L,
+                       bs, bd, (float)beta, (float)ambient, lg);
+  HIPK_CHECK(hipGetLastError());
+}
+
 // ---- convergence check (single lane) ------------------------------------------
 // last_only: the sweep's interior computed only its last residual (the
 // monotone check, fused_check_tail): the other slots only advance the count

@@ -220,7 +220,8 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   return false;
 }
 
-bool lean_supported(DType t, const KernelSpec& k, bool with_source, bool with_walls) {
+bool lean_supported(DType t, const KernelSpec& k, bool with_source, bool with_walls, bool with_convective) {
+  if (with_convective) return !with_source && k.kind == KernelSpec::TBL && lean_conv_dispatch(t, nullptr, k, nullptr);
   // (walls with a source run as single steps: no sweep form)
   if (with_walls) return !with_source && k.kind == KernelSpec::TBL && lean_wall_dispatch(t, nullptr, k, nullptr);
   if (with_source)
@@ -233,12 +234,15 @@ void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* st
   if (p.box.empty()) return;
   if (p.has_walls()) {
     // a sweep next to an insulated wall never falls back to Dirichlet arithmetic
-    const bool ok = !p.src && lean_wall_dispatch(t, &p, k, stream);
+    // (nor, next to a convective one, to insulated arithmetic)
+    const bool conv = p.has_convective();
+    const bool ok = !p.src && (conv ? lean_conv_dispatch(t, &p, k, stream) : lean_wall_dispatch(t, &p, k, stream));
     if (!ok) {
       const KernelSpec r = k.resolved(t);
-      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t)
-                                        << ") has no insulated-wall form" << (p.src ? " with a heat source" : "")
-                                        << "; with insulated walls use the default --kernel2 (tl2, tl3 or tl4 "
+      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t) << ") has no "
+                                        << (conv ? "convective-wall" : "insulated-wall") << " form"
+                                        << (p.src ? " with a heat source" : "")
+                                        << "; with insulated or convective walls use the default --kernel2 (tl2, tl3 or tl4 "
                                            "without shape fields)");
     }
     return;

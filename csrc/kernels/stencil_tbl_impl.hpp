@@ -90,6 +90,13 @@ struct TBLWalls {
   int x[2], y[2], z[2];
 };
 constexpr int kWallNoneLo = -(1 << 30), kWallNoneHi = 1 << 30;
+// Convective walls: the coefficient of each face in the same frame (0: an
+// insulated face, or none) and the ambient temperature, in the field's dtype
+template <typename Real>
+struct TBLConv {
+  Real x[2], y[2], z[2];
+  Real tinf;
+};
 
 namespace {
 
@@ -186,23 +193,41 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 #undef H3D_TBL_NAME
 #undef H3D_TBL_SRC
 #undef H3D_TBL_WALL
+// WALL 2: convective (Robin) walls (kernels.hpp StencilParams::wall_beta).  The
+// wall form's masked step with one more term: the neighbour across a wall is
+// the ghost fma(beta, T_inf - c, c) of that face, T_inf - c formed once per
+// row; beta = 0 (an insulated face of the same run) gives c.  The six
+// coefficients and the ambient arrive by value (TBLConv, uniform: SGPRs).  The
+// classification that keeps wall-adjacent waves, tiles and plane steps off the
+// mask-free step is the wall form's, unchanged.  A kernel of its own again
+// (stencil_tbl_conv, instantiated in stencil_tbl_conv.hip): insulated-only runs
+// keep stencil_tbl_wall.
+#define H3D_TBL_NAME stencil_tbl_conv
+#define H3D_TBL_SRC 0
+#define H3D_TBL_WALL 2
+#include "stencil_tbl_kernel.inc"
+#undef H3D_TBL_NAME
+#undef H3D_TBL_SRC
+#undef H3D_TBL_WALL
 
 // EW: the edge role of waves 0 and WY - 1 (0 = off, else 1 + their owned rows)
-// WALL: the insulated-wall form (p.wall; no source form, no edge role)
+// WALL: 1 the insulated-wall form (p.wall; no source form, no edge role), 2 the
+// convective-wall form (p.wall_beta, p.ambient as well)
 template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false, int EW = 0,
-          bool WALL = false>
+          int WALL = 0>
 void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
   constexpr bool swap_xy = SW;
   // (if constexpr: only the form that is launched gets instantiated)
   const void* kfn = [] {
     if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
-    else if constexpr (WALL) return reinterpret_cast<const void*>(&stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>);
+    else if constexpr (WALL == 2) return reinterpret_cast<const void*>(&stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>);
+    else if constexpr (WALL == 1) return reinterpret_cast<const void*>(&stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>);
     else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>);
   }();
   static_assert(EW == 0 || !SRC, "the edge role has no source form");
   static_assert(!WALL || (!SRC && EW == 0), "the wall form has no source form and no edge role");
   HEAT3D_CHECK(SRC == (p.src != nullptr), "tl: source form mismatch");
-  HEAT3D_CHECK(WALL == p.has_walls(), "tl: wall form mismatch");
+  HEAT3D_CHECK((WALL != 0) == p.has_walls() && (WALL == 2) == p.has_convective(), "tl: wall form mismatch");
   Box b = p.box;
   constexpr int TY = WY * R + 2 * (EW > 0 ? EW - 1 : 0);  // as the kernel's
   // swap_xy: march along y with x as the tile rows (thin x slabs: a tile of
@@ -264,6 +289,18 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       wl.z[e] = coord(p.wall[2][e], e);
     }
   }
+  // ... and the convective coefficients (an insulated face: 0)
+  TBLConv<Real> cv{};
+  {
+    auto beta = [&](int a, int e) { return (Real)(p.wall[a][e] != kNoWall && p.wall_beta[a][e] > 0 ? p.wall_beta[a][e] : 0); };
+    const int ax = swap_xy ? 1 : 0, ay = swap_xy ? 0 : 1;
+    for (int e = 0; e < 2; ++e) {
+      cv.x[e] = beta(ax, e);
+      cv.y[e] = beta(ay, e);
+      cv.z[e] = beta(2, e);
+    }
+    cv.tinf = (Real)p.ambient;
+  }
   constexpr int YS = TY - 2 * K;
   static const int slots = device_slots(kfn, 64 * WY);  // magic static: thread-safe under --gpus N
   constexpr int U = Q == 4 ? 12 : 6;  // the kernel's unroll (lcm(Q, 3, 2))
@@ -315,7 +352,11 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       hipLaunchKernelGGL((stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
                          static_cast<const Real*>(p.in), static_cast<Real*>(p.out), static_cast<const Real*>(p.src),
                          ga, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
-    else if constexpr (WALL)
+    else if constexpr (WALL == 2)
+      hipLaunchKernelGGL((stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
+                         static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, wl, cv, (Real)p.D[0],
+                         (Real)p.D[1], (Real)p.D[2], r, done);
+    else if constexpr (WALL == 1)
       hipLaunchKernelGGL((stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
                          static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, wl, (Real)p.D[0],
                          (Real)p.D[1], (Real)p.D[2], r, done);
@@ -334,6 +375,7 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       for (int z : {wide, aligned})
         if (std::find(zs_opts.begin(), zs_opts.end(), z) == zs_opts.end()) zs_opts.push_back(z);
       tune_schedule(SRC    ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src")
+                    : WALL == 2 ? (sizeof(Real) == 8 ? "tl-fp64-conv" : "tl-fp32-conv")
                     : WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall" : "tl-fp32-wall")
                     : sizeof(Real) == 8 ? "tl-fp64" : "tl-fp32",
                     kfn, box, slots, p.cu_reserved, U, zs_opts, s, fire,

@@ -6,7 +6,10 @@
 // stencil_tbl_wall, stencil_tbl_wall.hip) is the insulated-wall form: in the
 // masked step a neighbour across an insulated wall is replaced by the centre
 // value (impl.hpp), and a wave or plane step that holds a wall-adjacent row,
-// column or plane never takes the mask-free step.
+// column or plane never takes the mask-free step.  H3D_TBL_WALL 2 (kernel
+// stencil_tbl_conv, stencil_tbl_conv.hip) is the convective-wall form: the same
+// masked step, with the ghost fma(beta, T_inf - c, c) of the face (TBLConv) in
+// place of the centre value c; an insulated face enters with beta = 0.
 //
 // EW > 0: the edge role (impl.hpp, third step form).  Waves 0 and WY - 1 hold
 // the tile's K halo rows and E = EW - 1 owned rows next to them (R + E rows; the
@@ -20,6 +23,9 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
                                                        TBLArgs g,
 #if H3D_TBL_WALL
                                                        TBLWalls wa,
+#if H3D_TBL_WALL == 2
+                                                       TBLConv<Real> cv,
+#endif
 #endif
                                                        Real Dx, Real Dy, Real Dz,
                                                        unsigned long long* res, const int* done) {
@@ -298,6 +304,19 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         Real zm = dpp_shr1z(C[r]);
         Real zp = dpp_shl1z(C[r]);
         Real xm = M[r], xp = P[r];
+#if H3D_TBL_WALL == 2
+        if constexpr (!FAST) {
+          // the convective ghost of each face (kernels.hpp convective_ghost; beta
+          // 0: the mirror ghost of an insulated wall)
+          const Real da = cv.tinf - C[r];
+          if (wxm) xm = h3d_fma(cv.x[0], da, C[r]);
+          if (wxp) xp = h3d_fma(cv.x[1], da, C[r]);
+          if ((wyb >> r) & 1) ym = h3d_fma(cv.y[0], da, C[r]);
+          if ((wyb >> (RB + r)) & 1) yp = h3d_fma(cv.y[1], da, C[r]);
+          zm = zwm ? h3d_fma(cv.z[0], da, C[r]) : zm;
+          zp = zwp ? h3d_fma(cv.z[1], da, C[r]) : zp;
+        }
+#else
         if constexpr (!FAST) {
           // the mirror ghost: the neighbour across an insulated wall is the centre value
           if (wxm) xm = C[r];
@@ -307,6 +326,7 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
           zm = zwm ? C[r] : zm;
           zp = zwp ? C[r] : zp;
         }
+#endif
         // (SW: the rows are the x terms of the update, the marching axis its y terms)
         const Real nv = SW ? ftcs<Real>(C[r], ym, yp, xm, xp, zm, zp, Dx, Dy, Dz)
                            : ftcs<Real>(C[r], xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);

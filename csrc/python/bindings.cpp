@@ -22,6 +22,7 @@
 #include "../comm/net.hpp"
 #include "../core/config.hpp"
 #include "../core/decomp.hpp"
+#include "../kernels/cpu_rows.hpp"
 #include "../compat/reference_scheme.hpp"
 #include "../runtime/solver.hpp"
 
@@ -135,6 +136,14 @@ void set_walls(StencilParams& p, const std::array<int64_t, 6>& w) {
     for (int e = 0; e < 2; ++e) p.wall[a][e] = w[2 * a + e];
 }
 
+// conv = the coefficient of each face in the same order, negative where the face is not convective
+constexpr std::array<double, 6> kNoConv = {-1, -1, -1, -1, -1, -1};
+void set_conv(StencilParams& p, const std::array<double, 6>& c, double ambient) {
+  for (int a = 0; a < 3; ++a)
+    for (int e = 0; e < 2; ++e) p.wall_beta[a][e] = c[2 * a + e];
+  p.ambient = ambient;
+}
+
 StencilParams sparams(int64_t in_ptr, int64_t out_ptr, const std::array<int64_t, 3>& n,
                       int64_t esize, const std::array<int64_t, 6>& box,
                       const std::array<double, 3>& D, int64_t state_ptr, int slot) {
@@ -228,6 +237,11 @@ PYBIND11_MODULE(_heat3d, m) {
   m.attr("NO_WALL") = (int64_t)kNoWall;
   m.def("parse_insulated", &parse_insulated);
   m.def("insulated_str", &insulated_str);
+  m.def("parse_convective", &parse_convective);
+  m.def("convective_str", &convective_str);
+  m.def("lean_conv_supported", [](const std::string& dtype, const std::string& spec) {
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true, true);
+  }, py::arg("dtype"), py::arg("spec"));
   m.def("lean_wall_supported", [](const std::string& dtype, const std::string& spec) {
     return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true);
   }, py::arg("dtype"), py::arg("spec"));
@@ -431,6 +445,10 @@ PYBIND11_MODULE(_heat3d, m) {
     d["output"] = c.output;
     d["compat"] = c.compat;
     d["banner"] = c.echo_banner();
+    d["insulated"] = insulated_str(c.insulated);
+    d["convective"] = convective_str(c.convective);
+    d["convective_beta"] = c.convective;
+    d["ambient"] = c.ambient;
     return d;
   });
   m.def("physics", [](int64_t nx, int64_t ny, int64_t nz) {
@@ -526,7 +544,7 @@ PYBIND11_MODULE(_heat3d, m) {
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                               int64_t stream, int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -538,12 +556,14 @@ PYBIND11_MODULE(_heat3d, m) {
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
+    set_conv(p, conv, ambient);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
-     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
+     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
   hk.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h, int64_t stream) {
     DType t = dt_of(dt);
@@ -581,16 +601,45 @@ PYBIND11_MODULE(_heat3d, m) {
   ck.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
                        int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
+    set_conv(p, conv, ambient);
     py::gil_scoped_release nogil;
     cpu::stencil(t, p);
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
-     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
+     py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
+  // one row of the convective-wall update in either build of the row kernels
+  // (cpu_rows.hpp; "fma" needs a CPU with FMA + AVX2: see cpu.has_fma): off =
+  // element offsets of the x-, x+, y-, y+ neighbours (0: across a wall), kz =
+  // the row indices whose z- / z+ neighbour is; returns the row's max residual
+  ck.def("has_fma", []() {
+    __builtin_cpu_init();
+    return __builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2");
+  });
+  ck.def("conv_row", [](const std::string& build, const std::string& dt, int64_t in_ptr, int64_t out_ptr, int64_t n,
+                        std::array<int64_t, 4> off, std::array<int64_t, 2> kz, std::array<double, 6> beta,
+                        double ambient, std::array<double, 3> D) {
+    const bool fma = build == "fma";
+    if (!fma && build != "generic") throw UsageError("conv_row: build is fma or generic");
+    if (dt_of(dt) == DType::F64) {
+      double b[6];
+      for (int f = 0; f < 6; ++f) b[f] = beta[f];
+      auto fn = fma ? cpu::rows_fma::ftcs_row_conv_f64 : cpu::rows_generic::ftcs_row_conv_f64;
+      return fn(reinterpret_cast<const double*>(in_ptr), reinterpret_cast<double*>(out_ptr), n, off[0], off[1], off[2],
+                off[3], kz[0], kz[1], b, ambient, D[0], D[1], D[2]);
+    }
+    float b[6];
+    for (int f = 0; f < 6; ++f) b[f] = (float)beta[f];
+    auto fn = fma ? cpu::rows_fma::ftcs_row_conv_f32 : cpu::rows_generic::ftcs_row_conv_f32;
+    return fn(reinterpret_cast<const float*>(in_ptr), reinterpret_cast<float*>(out_ptr), n, off[0], off[1], off[2],
+              off[3], kz[0], kz[1], b, (float)ambient, (float)D[0], (float)D[1], (float)D[2]);
+  }, py::arg("build"), py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("off"),
+     py::arg("kz"), py::arg("beta"), py::arg("ambient"), py::arg("D"));
   ck.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
@@ -613,7 +662,7 @@ PYBIND11_MODULE(_heat3d, m) {
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                               int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -625,13 +674,15 @@ PYBIND11_MODULE(_heat3d, m) {
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
+    set_conv(p, conv, ambient);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
     py::gil_scoped_release nogil;
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
-     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls);
+     py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
   ck.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h) {
     DType t = dt_of(dt);

@@ -104,6 +104,10 @@ class Backend {
                           StreamId s) = 0;
   virtual void copy_box(DType t, const void* src, const Layout& Ls, const Box& bs, void* dst,
                         const Layout& Ld, const Box& bd, StreamId s) = 0;
+  // a convective wall plane (box bd of field f) <- the ghost values
+  // convective_ghost(c, beta, ambient) of the first interior plane (box bs)
+  virtual void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,
+                                  double ambient, StreamId s) = 0;
   // convergence checks of `count` consecutive iterations, residual slots
   // slot .. slot + count - 1, in order (one launch on the GPU)
   // last_only: every slot but the last only advances the count (Solver::residual_last_ok)

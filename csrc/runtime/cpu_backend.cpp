@@ -97,6 +97,10 @@ class CpuBackend final : public Backend {
                 const Layout& Ld, const Box& bd, StreamId) override {
     cpu::copy_box(t, src, Ls, bs, dst, Ld, bd);
   }
+  void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta, double ambient,
+                          StreamId) override {
+    cpu::refresh_convective(t, f, L, bs, bd, beta, ambient);
+  }
   void check_convergence(DeviceState* st, int slot, StreamId, int count, bool last_only) override {
     HEAT3D_CHECK(!last_only, "cpu backend: no last-residual sweeps");
     for (int i = 0; i < count; ++i) cpu::check_convergence(st, slot + i);

@@ -469,6 +469,10 @@ class HipBackend final : public Backend {
                 const Layout& Ld, const Box& bd, StreamId s) override {
     op(s, [&](hipStream_t st) { hip::copy_box(t, src, Ls, bs, dst, Ld, bd, st); });
   }
+  void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta, double ambient,
+                          StreamId s) override {
+    op(s, [&](hipStream_t st) { hip::refresh_convective(t, f, L, bs, bd, beta, ambient, st); });
+  }
   void delay(double us, StreamId s, int blocks) override {
     op(s, [&](hipStream_t st) { hip::delay(us, st, blocks, fat_comm_); });
   }

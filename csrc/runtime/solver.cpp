@@ -236,7 +236,10 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
     kspec2_.kind = KernelSpec::TBL;
     kspec2_.K = k2;
   }
-  walls_ = cfg_.insulated & 0x3fu;
+  conv_ = convective_mask(cfg_.convective);
+  HEAT3D_CHECK(!(conv_ & cfg_.insulated), "a face is either insulated or convective");
+  for (int f = 0; f < 6; ++f) conv_beta_[f] = ((conv_ >> f) & 1u) ? cfg_.convective[f] : -1.0;
+  walls_ = (cfg_.insulated | conv_) & 0x3fu;
   // Single steps next to insulated walls refresh the wall planes first, on
   // the one stream that then runs the halo and the step: the single-step
   // schedule of a wall run is not overlapped.  The sweeps are (tb_overlap_
@@ -547,11 +550,17 @@ void Solver::preflight_extra_field(const char* what, std::size_t extra) {
   planned_bytes_ += extra;
 }
 
-bool Solver::lean_ok(const KernelSpec& ks) const { return hip::lean_supported(dt_, ks, has_source_, walls_ != 0); }
+bool Solver::lean_ok(const KernelSpec& ks) const {
+  return hip::lean_supported(dt_, ks, has_source_, walls_ != 0, conv_ != 0);
+}
 
 void Solver::set_walls(StencilParams& sp, const Local& l) const {
   for (int a = 0; a < 3; ++a)
-    for (int e = 0; e < 2; ++e) sp.wall[a][e] = l.wall[a][e];
+    for (int e = 0; e < 2; ++e) {
+      sp.wall[a][e] = l.wall[a][e];
+      sp.wall_beta[a][e] = conv_beta_[2 * a + e];
+    }
+  sp.ambient = cfg_.ambient;
 }
 
 void Solver::refresh_walls(int b, StreamId s) {
@@ -582,7 +591,12 @@ void Solver::refresh_walls(int b, StreamId s) {
           bs.hi[c] = bd.hi[c] = std::min(l.sd.n[c] + gc, ghi - l.sd.gstart[c]);
           empty |= bs.hi[c] <= bs.lo[c];
         }
-        if (!empty) be_->copy_box(dt_, l.field[b], l.L, bs, l.field[b], l.L, bd, s);
+        if (empty) continue;
+        // a convective wall shows the ghost of its inward neighbour, an insulated one a copy
+        if ((conv_ >> (2 * a + e)) & 1u)
+          be_->refresh_convective(dt_, l.field[b], l.L, bs, bd, conv_beta_[2 * a + e], cfg_.ambient, s);
+        else
+          be_->copy_box(dt_, l.field[b], l.L, bs, l.field[b], l.L, bd, s);
       }
 }
 

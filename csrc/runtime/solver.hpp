@@ -321,7 +321,14 @@ class Solver {
   // refreshed from their inward neighbours (refresh_walls), which gives the
   // same bits.  With a source or a conductivity as well there is no sweep
   // form: every iteration is such a single step (walls_single).
-  unsigned walls_ = 0;
+  // Convective walls (Config::convective, ambient) are walls in all of this:
+  // walls_ holds the insulated and the convective faces, conv_ the convective
+  // ones with their coefficients in conv_beta_.  Their sweeps run the
+  // convective forms of the lean kernel (StencilParams::wall_beta; insulated
+  // faces of the same run enter as coefficient 0), their single steps refresh
+  // the wall plane with the ghost values (Backend::refresh_convective).
+  unsigned walls_ = 0, conv_ = 0;
+  double conv_beta_[6] = {-1, -1, -1, -1, -1, -1};
   bool walls_single() const { return walls_ && (has_source_ || has_cond_); }
   void set_walls(StencilParams& sp, const Local& l) const;
   // wall planes of buffer b <- their inward neighbours, axis order x, y, z,

@@ -419,7 +419,12 @@ void Solver::save_checkpoint(const std::string& dir) {
     j.set_raw("has_source", has_source_ ? "true" : "false");
     // nor the conductivity field
     j.set_raw("has_conductivity", has_cond_ ? "true" : "false");
-    j.set("insulated", insulated_str(walls_));
+    j.set("insulated", insulated_str(walls_ & ~conv_));
+    // (only runs with a convective face write these keys)
+    if (conv_) {
+      j.set("convective", convective_str(cfg_.convective));
+      j.set("ambient", ambient_str(cfg_.ambient));
+    }
     io::write_file_atomic(dir + "/meta.json", j.dump() + "\n");
     // older field files, and the temp files of saves that a crash
     // interrupted (a full-grid field.<iter>.raw.tmp each)
@@ -453,8 +458,20 @@ void Solver::load_checkpoint(const std::string& dir) {
   // (checkpoints older than the insulated walls have no such key: all Dirichlet)
   {
     const std::string was = meta.count("insulated") ? meta["insulated"] : std::string("none");
-    HEAT3D_CHECK(was == insulated_str(walls_), "checkpoint " << dir << " was written with --insulated " << was
-                                                               << ", this run has --insulated " << insulated_str(walls_));
+    const std::string now = insulated_str(walls_ & ~conv_);
+    HEAT3D_CHECK(was == now, "checkpoint " << dir << " was written with --insulated " << was
+                                           << ", this run has --insulated " << now);
+    // (nor the convective keys: no convective face)
+    const std::string cwas = meta.count("convective") ? meta["convective"] : std::string("none");
+    const std::string cnow = convective_str(cfg_.convective);
+    HEAT3D_CHECK(cwas == cnow, "checkpoint " << dir << " was written with --convective " << cwas
+                                             << ", this run has --convective " << cnow);
+    if (conv_) {
+      const std::string awas = meta.count("ambient") ? meta["ambient"] : std::string("0");
+      HEAT3D_CHECK(awas == ambient_str(cfg_.ambient), "checkpoint " << dir << " was written with --ambient " << awas
+                                                                      << ", this run has --ambient "
+                                                                      << ambient_str(cfg_.ambient));
+    }
   }
   const int64_t it = std::atoll(meta["iteration"].c_str());
   const double norm = std::atof(meta["norm"].c_str());

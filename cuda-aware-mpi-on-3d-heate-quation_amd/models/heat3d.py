@@ -121,6 +121,38 @@ class HeatEquation3D:
         g = 1.0 - 4.0 * self.D[axis] * np.sin(np.pi * m / (2.0 * M)) ** 2
         return T, float(g)
 
+    def wall_coefficient(self, h: float, axis: int, k: float = 1.0) -> float:
+        """Coefficient beta of a convective wall of ``axis`` for a surface
+        coefficient ``h`` (-k dT/dn = h (T - T_inf)) and a conductivity ``k``:
+        beta = 2 Bi / (2 + Bi) with Bi = h * h_axis / k, the surface acting at
+        the face midway between the wall vertex and the first interior vertex.
+        The update stays a convex combination only for beta <= 1 (Bi <= 2): a
+        larger one raises ValueError (refine the grid along ``axis``)."""
+        if not (h >= 0.0 and k > 0.0 and np.isfinite(h) and np.isfinite(k)):
+            raise ValueError(f"wall_coefficient: need h >= 0 and k > 0, got h = {h}, k = {k}")
+        bi = float(h) * self.h[axis] / float(k)
+        beta = 2.0 * bi / (2.0 + bi)
+        if beta > 1.0:
+            raise ValueError(f"wall_coefficient: Bi = {bi:g} gives beta = {beta:g} > 1 (need Bi <= 2)")
+        return beta
+
+    def convective_slab_steady(self, beta: float, ambient: float = 0.0) -> np.ndarray:
+        """Exact steady state of the discrete scheme for the slab problem: x-, x+,
+        z-, z+ insulated, y- convective with coefficient ``beta`` > 0 and ambient
+        ``ambient``, y+ Dirichlet at 1.  Constant in x and z and linear in y,
+        T_j = T_inf + s (1 / beta + j - 1) for j = 1 .. Ny - 2 with
+        s = (1 - T_inf) / (1 / beta + Ny - 2); the y- wall vertices hold the
+        ghost T_1 + beta (T_inf - T_1) (global array)."""
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"convective_slab_steady: beta {beta} outside (0, 1]")
+        Ny = self.n[1]
+        s = (1.0 - ambient) / (1.0 / beta + Ny - 2)
+        j = np.arange(Ny, dtype=np.float64)
+        v = ambient + s * (1.0 / beta + j - 1.0)
+        v[0] = v[1] + beta * (ambient - v[1])
+        v[-1] = 1.0
+        return np.broadcast_to(v[None, :, None], self.n).copy()
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -148,7 +180,7 @@ class HeatSolver:
                  check_every: int = 64, graph_chunk: int = 0, device: Optional[int] = None,
                  threads: int = 0, extra_args: Sequence[str] = (), group=None,
                  phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False,
-                 insulated=None):
+                 insulated=None, convective=None, ambient: float = 0.0):
         ext = native()
         self.model = HeatEquation3D(tuple(int(v) for v in n))  # type: ignore[arg-type]
         args: List[str] = [str(int(v)) for v in n] + [str(int(iter_max)), _fmt(eps)]
@@ -173,6 +205,14 @@ class HeatSolver:
             # zero-flux walls: names of x-, x+, y-, y+, z-, z+ (a sequence or a comma list) or "all";
             # the native parser validates them (UsageError)
             args += ["--insulated", insulated if isinstance(insulated, str) else ",".join(str(f) for f in insulated)]
+        if convective:
+            # convective (Robin) walls: {"y-": 0.5, "x+": 0.25} (or "all"), a string "y-=0.5,x+=0.25";
+            # the native parser validates faces and coefficients (UsageError)
+            text = convective if isinstance(convective, str) else ",".join(
+                f"{f}={float(b)!r}" for f, b in dict(convective).items())
+            args += ["--convective", text]
+        if ambient != 0.0 or convective:
+            args += ["--ambient", repr(float(ambient))]
         args += list(extra_args)
         self.args = args
 

@@ -111,6 +111,30 @@ def insulated_mask(insulated) -> int:
     return native().parse_insulated(text) if text else 0
 
 
+def convective_faces(convective) -> list:
+    """Coefficient per face (x-, x+, y-, y+, z-, z+; -1.0 where the face is not
+    convective) of ``convective``: None, a mapping ``{"y-": 0.5, "x+": 0.25}``
+    (``"all"`` is a key too), a string ``"y-=0.5,x+=0.25"`` or a sequence of six
+    numbers.  Unknown faces and coefficients outside [0, 1] are the native
+    UsageError."""
+    if convective is None:
+        return [-1.0] * 6
+    if isinstance(convective, str):
+        return list(native().parse_convective(convective)) if convective else [-1.0] * 6
+    if hasattr(convective, "items"):
+        text = ",".join(f"{k}={float(v)!r}" for k, v in convective.items())
+        return list(native().parse_convective(text)) if text else [-1.0] * 6
+    out = [float(v) for v in convective]
+    if len(out) != 6:
+        raise ValueError("convective: six coefficients, one per face")
+    return out
+
+
+def convective_mask(convective) -> int:
+    """Face mask (bit 2 * axis + side) of the convective faces."""
+    return sum(1 << f for f, b in enumerate(convective_faces(convective)) if b >= 0)
+
+
 def wall_coords(mask: int, n: Sequence[int], gstart: Sequence[int] = (1, 1, 1),
                 N: Optional[Sequence[int]] = None) -> list:
     """``walls`` argument of the kernels: per face the local coordinate of the
@@ -130,12 +154,14 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
               state: Optional[torch.Tensor] = None, slot: int = 0,
               source: Optional[PaddedField] = None,
               conductivity: Optional[PaddedField] = None,
-              walls: Optional[Sequence[int]] = None) -> None:
+              walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> None:
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
 
     ``walls``: insulated walls as ``wall_coords`` gives them (CPU tensors only,
     without source / conductivity: the single-step gfx950 kernels run on wall
-    planes copied from their inward neighbours instead).
+    planes copied from their inward neighbours instead).  ``conv``: the faces
+    among them that are convective (``convective_faces`` forms), with the
+    ambient temperature ``ambient``.
 
     ``source``: optional field S = dtype(dt * q) in the same layout, added to
     every updated point (kernels.hpp ftcs_update_src).
@@ -171,7 +197,8 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
                         kernel, _stream_ptr(src.flat), qptr, cptr)
     else:
         w = list(walls) if walls is not None else [ext.NO_WALL] * 6
-        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr, w)
+        ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr, w,
+                        convective_faces(conv), float(ambient))
 
 
 def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: str = "auto",
@@ -231,7 +258,7 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
            kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0,
            source: Optional[PaddedField] = None, conductivity: Optional[PaddedField] = None,
-           walls: Optional[Sequence[int]] = None) -> None:
+           walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> None:
     """K-step sweep with deep ghosts on every axis (the block-decomposition
     schedule): ``u`` = (ux0, ux1, uy0, uy1, uz0, uz1) are the update ranges of
     the intermediate steps.  GPU tensors run the lean kernel, CPU tensors the
@@ -239,7 +266,10 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     same layout (deep ghosts included), added at every step.  ``conductivity``:
     as in ``sweep`` (GPU: ``tv2`` / ``tv3``).  ``walls``: insulated walls as
     ``wall_coords`` gives them; GPU tensors run the wall form of the lean
-    kernel (stencil_tbl_wall.hip; a spec without one is a RuntimeError)."""
+    kernel (stencil_tbl_wall.hip; a spec without one is a RuntimeError).
+    ``conv``: the faces among ``walls`` that are convective (``convective_faces``
+    forms: the coefficient per face) with the ambient temperature ``ambient``;
+    GPU tensors then run the convective form (stencil_tbl_conv.hip)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -253,9 +283,9 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     cptr = _cond_ptr(src, conductivity)
     w = list(walls) if walls is not None else [native().NO_WALL] * 6
     if src.device.type == "cuda":
-        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr, w)
+        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr, w, convective_faces(conv), float(ambient))
     else:
-        native().cpu.stencil_sweep3(*args, qptr, cptr, w)
+        native().cpu.stencil_sweep3(*args, qptr, cptr, w, convective_faces(conv), float(ambient))
 
 
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
@@ -277,13 +307,19 @@ def unpack_box(f: PaddedField, box: Sequence[int], buf: torch.Tensor) -> None:
 
 
 def ftcs_reference(T: torch.Tensor, D: Sequence[float], src: Optional[torch.Tensor] = None,
-                   cond: Optional[torch.Tensor] = None, insulated=None) -> Tuple[torch.Tensor, float]:
+                   cond: Optional[torch.Tensor] = None, insulated=None, convective=None,
+                   ambient: float = 0.0) -> Tuple[torch.Tensor, float]:
     """Plain-PyTorch FTCS on a ghosted block; returns (new interior, max |dT|).
 
     ``insulated``: faces of the block that are zero-flux walls (``insulated_mask``
     forms; the block is the whole grid).  The ghost plane of such a face is
     replaced by a copy of the first interior plane before the update, so the
     neighbour across the wall is the centre value.
+
+    ``convective``: faces that are convective walls (``convective_faces`` forms)
+    with the ambient temperature ``ambient``: the ghost plane becomes
+    fma(beta, T_inf - c, c) of the first interior plane c (kernels.hpp
+    convective_ghost), beta and T_inf rounded to the dtype of ``T``.
 
     ``cond``: optional ghosted block (shape of ``T``) of Ch = dtype(0.5 * c),
     c the relative conductivity: the update of kernels.hpp ftcs_update_var.
@@ -294,13 +330,25 @@ def ftcs_reference(T: torch.Tensor, D: Sequence[float], src: Optional[torch.Tens
 
     Same arithmetic as the native backends (exactly rounded FMAs emulated with
     error-free transformations, utils/fma.py), so results compare bitwise."""
-    from ..utils.fma import ftcs_update, ftcs_update_var
+    from ..utils.fma import fma, ftcs_update, ftcs_update_var
 
     def seven(F):
         return (F[1:-1, 1:-1, 1:-1], F[:-2, 1:-1, 1:-1], F[2:, 1:-1, 1:-1], F[1:-1, :-2, 1:-1], F[1:-1, 2:, 1:-1],
                 F[1:-1, 1:-1, :-2], F[1:-1, 1:-1, 2:])
 
     mask = insulated_mask(insulated)
+    beta = convective_faces(convective)
+    if any(b >= 0 for b in beta):
+        T = T.clone()
+        tinf = torch.tensor(float(ambient), dtype=T.dtype)
+        for f, b in enumerate(beta):
+            if b < 0:
+                continue
+            if (mask >> f) & 1:
+                raise ValueError("a face is either insulated or convective")
+            a, e = divmod(f, 2)
+            c1 = T.select(a, T.shape[a] - 2 if e else 1).clone()
+            T.select(a, T.shape[a] - 1 if e else 0).copy_(fma(b, tinf - c1, c1))
     if mask:
         T = T.clone()
         for a in range(3):
