@@ -146,6 +146,7 @@ static int drive(const Config& cfg, Solver& solver) {
                           ", " + std::to_string(d.topo.dims[2]) + "]");
     j.set("kernel", solver.kernel_name());
     j.set_bool("conductivity_sweeps", cfg.cond_sweeps);
+    j.set_bool("wall_source_sweeps", cfg.wall_source_sweeps);
     j.set("insulated", insulated_str(cfg.insulated));
     j.set("convective", convective_str(cfg.convective));
     j.set("ambient", cfg.ambient);

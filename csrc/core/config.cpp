@@ -206,6 +206,8 @@ std::string Config::usage() {
      << "  --ambient T               the ambient temperature T_inf of the convective walls (default 0)\n"
      << "  --conductivity-sweeps     with a conductivity field: K-step sweeps of the tv kernels (tv2 / tv3,\n"
      << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
+     << "  --wall-source-sweeps      with insulated or convective walls and a heat source: K-step sweeps of the\n"
+     << "                            wall forms with a source instead of single steps; same bits (not with --compat)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -353,6 +355,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--initial") c.initial_file = get("--initial");
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
+    else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
     else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
     else if (key == "--convective") c.convective = parse_convective(get("--convective"));
     else if (key == "--ambient") {
@@ -487,6 +490,8 @@ Config Config::parse(int argc, const char* const* argv) {
                      insulated_str(convective_mask(c.convective) & c.insulated));
   if (c.cond_sweeps && c.compat)
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
+  if (c.wall_source_sweeps && c.compat)
+    throw UsageError("--wall-source-sweeps is not part of --compat (the reference has neither walls nor a source)");
   return c;
 }
 

@@ -69,6 +69,11 @@ struct Config {
   // --conductivity-sweeps: with a conductivity field, K-step sweeps of the tv
   // kernel family (stencil_tbv.hip) instead of single steps.  Off by default.
   bool cond_sweeps = false;
+  // --wall-source-sweeps: with insulated or convective walls and a heat source,
+  // K-step sweeps of the lean kernel's wall forms with a source
+  // (stencil_tbl_wall_src.hip, stencil_tbl_conv_src.hip) instead of single
+  // steps.  Off by default; without walls or without a source it does nothing.
+  bool wall_source_sweeps = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   // --insulated: faces of the global grid that are zero-flux walls instead of

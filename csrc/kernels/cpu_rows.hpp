@@ -46,6 +46,16 @@ using FtcsRowConvFn = double (*)(const Real* in, Real* out, int64_t n, int64_t o
                                  int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf, Real Dx, Real Dy,
                                  Real Dz);
 
+// walls with a heat source: FtcsRowWallFn / FtcsRowConvFn with src[k] added to
+// the finished update (ftcs_update_src; the ghost substitution comes first)
+template <typename Real>
+using FtcsRowWallSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t oxm, int64_t oxp,
+                                    int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz);
+template <typename Real>
+using FtcsRowConvSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t oxm, int64_t oxp,
+                                    int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf,
+                                    Real Dx, Real Dy, Real Dz);
+
 struct RowKernels {
   FtcsRowFn<double> f64;
   FtcsRowFn<float> f32;
@@ -58,6 +68,10 @@ struct RowKernels {
   FtcsRowWallFn<float> wall_f32;
   FtcsRowConvFn<double> conv_f64;
   FtcsRowConvFn<float> conv_f32;
+  FtcsRowWallSrcFn<double> wall_src_f64;
+  FtcsRowWallSrcFn<float> wall_src_f32;
+  FtcsRowConvSrcFn<double> conv_src_f64;
+  FtcsRowConvSrcFn<float> conv_src_f32;
 };
 
 const RowKernels& cpu_row_kernels();
@@ -79,6 +93,14 @@ double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int6
                          const double*, double, double, double, double);
 double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                          const float*, float, float, float, float);
+double ftcs_row_wall_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, double, double, double);
+double ftcs_row_wall_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, float, float, float);
+double ftcs_row_conv_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, const double*, double, double, double, double);
+double ftcs_row_conv_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, const float*, float, float, float, float);
 }  // namespace rows_generic
 namespace rows_fma {
 double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
@@ -97,6 +119,14 @@ double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int6
                          const double*, double, double, double, double);
 double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
                          const float*, float, float, float, float);
+double ftcs_row_wall_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, double, double, double);
+double ftcs_row_wall_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, float, float, float);
+double ftcs_row_conv_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, const double*, double, double, double, double);
+double ftcs_row_conv_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, const float*, float, float, float, float);
 }  // namespace rows_fma
 
 }  // namespace cpu

@@ -98,10 +98,11 @@ struct StencilParams {
   // ghost; the flux through the face between them is exactly 0) and the update
   // is evaluated as ever.  Taken from global indices, so it also holds for
   // wall-adjacent points computed inside a neighbour's deep halo.  cpu::stencil
-  // and cpu::stencil_multi honour it (without source / conductivity: those run
-  // as single steps on wall planes copied from their inward neighbours), as do
-  // the wall forms of the lean sweep (stencil_tbl_wall.hip); the single-step
-  // gfx950 kernels do not take it.
+  // and cpu::stencil_multi honour it, also with a source (not with a
+  // conductivity: that runs as single steps on wall planes copied from their
+  // inward neighbours), as do the wall forms of the lean sweep
+  // (stencil_tbl_wall.hip; with a source stencil_tbl_wall_src.hip); the
+  // single-step gfx950 kernels do not take it.
   int64_t wall[3][2] = {{kNoWall, kNoWall}, {kNoWall, kNoWall}, {kNoWall, kNoWall}};
   bool has_walls() const {
     for (int a = 0; a < 3; ++a)
@@ -116,7 +117,8 @@ struct StencilParams {
   // c; beta = 0 gives c, the insulated wall.  Once any face is convective the
   // insulated faces of the same call are evaluated as coefficient 0 (every
   // backend alike).  Honoured where `wall` is: cpu::stencil / stencil_multi and
-  // the convective forms of the lean sweep (stencil_tbl_conv.hip).
+  // the convective forms of the lean sweep (stencil_tbl_conv.hip; with a source
+  // stencil_tbl_conv_src.hip).
   double wall_beta[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
   double ambient = 0;
   bool has_convective() const {
@@ -190,14 +192,18 @@ bool lean_pair_supported(DType t, const KernelSpec& k);
 int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, int U, int L, int esize);
 // Is the lean kernel variant that k resolves to for dtype t instantiated?
 // with_source: its heat-source form (StencilParams::src != nullptr)
-// with_walls: its insulated-wall form (StencilParams::has_walls; no source form)
+// with_walls: its insulated-wall form (StencilParams::has_walls)
 // with_convective: its convective-wall form (StencilParams::has_convective; implies walls)
+// with_source and walls: the wall or convective form with a source
 bool lean_supported(DType t, const KernelSpec& k, bool with_source = false, bool with_walls = false,
                     bool with_convective = false);
 // the wall forms' dispatch (stencil_tbl_wall.hip); p == nullptr: only report
 bool lean_wall_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
 // the convective forms' (stencil_tbl_conv.hip)
 bool lean_conv_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
+// the same two with a heat source (stencil_tbl_wall_src.hip, stencil_tbl_conv_src.hip)
+bool lean_wall_src_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
+bool lean_conv_src_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
 // Convective walls on single steps: dst box (one wall plane) <- the ghost value
 // convective_ghost of the src box (the first interior plane), same field
 void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,

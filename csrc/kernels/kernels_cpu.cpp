@@ -90,16 +90,24 @@ static void stencil_t(const StencilParams& p) {
     if constexpr (sizeof(Real) == 8) return cpu_row_kernels().conv_f64;
     else return cpu_row_kernels().conv_f32;
   }();
+  const auto rowwallsrc = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().wall_src_f64;
+    else return cpu_row_kernels().wall_src_f32;
+  }();
+  const auto rowconvsrc = [] {
+    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().conv_src_f64;
+    else return cpu_row_kernels().conv_src_f32;
+  }();
   // convective walls (StencilParams::wall_beta): the coefficients in the
   // field's dtype, 0 on the insulated faces of the same call
   const bool conv = p.has_convective();
   Real beta[6];
   for (int f = 0; f < 6; ++f) beta[f] = static_cast<Real>(p.wall_beta[f / 2][f % 2] > 0 ? p.wall_beta[f / 2][f % 2] : 0);
   const Real tinf = static_cast<Real>(p.ambient);
-  // insulated walls (StencilParams::wall): the uniform update only
+  // insulated walls (StencilParams::wall): the uniform update, with or without a source
   const bool walls = p.has_walls();
-  HEAT3D_CHECK(!walls || (!p.src && !p.cond),
-               "cpu::stencil: insulated / convective walls with a source or a conductivity run as single steps on copied wall "
+  HEAT3D_CHECK(!walls || !p.cond,
+               "cpu::stencil: insulated / convective walls with a conductivity run as single steps on copied wall "
                "planes, not through StencilParams::wall");
   const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
   const Real* __restrict cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
@@ -110,6 +118,16 @@ static void stencil_t(const StencilParams& p) {
       const int64_t c = L.index(i, j, b.lo[2]);
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
       const double lres = nk <= 0 ? 0.0
+                          : conv && src
+                              ? rowconvsrc(in + c, out + c, src + c, nk, i == p.wall[0][0] ? 0 : -sx,
+                                           i == p.wall[0][1] ? 0 : sx, j == p.wall[1][0] ? 0 : -sy,
+                                           j == p.wall[1][1] ? 0 : sy, p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2],
+                                           beta, tinf, Dx, Dy, Dz)
+                          : walls && src
+                              ? rowwallsrc(in + c, out + c, src + c, nk, i == p.wall[0][0] ? 0 : -sx,
+                                           i == p.wall[0][1] ? 0 : sx, j == p.wall[1][0] ? 0 : -sy,
+                                           j == p.wall[1][1] ? 0 : sy, p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2],
+                                           Dx, Dy, Dz)
                           : conv  ? rowconv(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
                                             j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
                                             p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], beta, tinf, Dx, Dy, Dz)

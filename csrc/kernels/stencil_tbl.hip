@@ -221,9 +221,13 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
 }
 
 bool lean_supported(DType t, const KernelSpec& k, bool with_source, bool with_walls, bool with_convective) {
-  if (with_convective) return !with_source && k.kind == KernelSpec::TBL && lean_conv_dispatch(t, nullptr, k, nullptr);
-  // (walls with a source run as single steps: no sweep form)
-  if (with_walls) return !with_source && k.kind == KernelSpec::TBL && lean_wall_dispatch(t, nullptr, k, nullptr);
+  // (walls with a source: forms of their own, stencil_tbl_wall_src.hip / stencil_tbl_conv_src.hip)
+  if (with_convective)
+    return k.kind == KernelSpec::TBL && (with_source ? lean_conv_src_dispatch(t, nullptr, k, nullptr)
+                                                     : lean_conv_dispatch(t, nullptr, k, nullptr));
+  if (with_walls)
+    return k.kind == KernelSpec::TBL && (with_source ? lean_wall_src_dispatch(t, nullptr, k, nullptr)
+                                                     : lean_wall_dispatch(t, nullptr, k, nullptr));
   if (with_source)
     return t == DType::F64 ? dispatch_tbl_src<double>(nullptr, k, nullptr) : dispatch_tbl_src<float>(nullptr, k, nullptr);
   return t == DType::F64 ? dispatch_tbl<double>(nullptr, k, nullptr) : dispatch_tbl<float>(nullptr, k, nullptr);
@@ -236,7 +240,8 @@ void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* st
     // a sweep next to an insulated wall never falls back to Dirichlet arithmetic
     // (nor, next to a convective one, to insulated arithmetic)
     const bool conv = p.has_convective();
-    const bool ok = !p.src && (conv ? lean_conv_dispatch(t, &p, k, stream) : lean_wall_dispatch(t, &p, k, stream));
+    const bool ok = p.src ? (conv ? lean_conv_src_dispatch(t, &p, k, stream) : lean_wall_src_dispatch(t, &p, k, stream))
+                          : (conv ? lean_conv_dispatch(t, &p, k, stream) : lean_wall_dispatch(t, &p, k, stream));
     if (!ok) {
       const KernelSpec r = k.resolved(t);
       HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t) << ") has no "

@@ -209,23 +209,50 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 #undef H3D_TBL_NAME
 #undef H3D_TBL_SRC
 #undef H3D_TBL_WALL
+// SRC with WALL 1 / 2: an internally heated body behind insulated or convective
+// walls.  The wall form's masked step with the source form's re-loaded source
+// rows (the same clamped plane and roff[] offsets): the ghost substitution first,
+// then the update, then the source, which is the order of the single-step path
+// (wall planes refreshed, then ftcs_update_src).  The mask-free step is the
+// source form's.  Kernels of their own once more (stencil_tbl_wall_src and
+// stencil_tbl_conv_src, instantiated in stencil_tbl_wall_src.hip and
+// stencil_tbl_conv_src.hip), so the six kernels above keep their code; the
+// shapes that fit the register budget are in profiles/wall_source_sweeps.md.
+#define H3D_TBL_NAME stencil_tbl_wall_src
+#define H3D_TBL_SRC 1
+#define H3D_TBL_WALL 1
+#include "stencil_tbl_kernel.inc"
+#undef H3D_TBL_NAME
+#undef H3D_TBL_SRC
+#undef H3D_TBL_WALL
+#define H3D_TBL_NAME stencil_tbl_conv_src
+#define H3D_TBL_SRC 1
+#define H3D_TBL_WALL 2
+#include "stencil_tbl_kernel.inc"
+#undef H3D_TBL_NAME
+#undef H3D_TBL_SRC
+#undef H3D_TBL_WALL
 
 // EW: the edge role of waves 0 and WY - 1 (0 = off, else 1 + their owned rows)
-// WALL: 1 the insulated-wall form (p.wall; no source form, no edge role), 2 the
-// convective-wall form (p.wall_beta, p.ambient as well)
+// WALL: 1 the insulated-wall form (p.wall; no edge role), 2 the convective-wall
+// form (p.wall_beta, p.ambient as well); either with SRC: their source forms
 template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = false, bool SRC = false, int EW = 0,
           int WALL = 0>
 void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
   constexpr bool swap_xy = SW;
   // (if constexpr: only the form that is launched gets instantiated)
   const void* kfn = [] {
-    if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
+    if constexpr (SRC && WALL == 2)
+      return reinterpret_cast<const void*>(&stencil_tbl_conv_src<Real, R, WY, K, Q, NTS, SW>);
+    else if constexpr (SRC && WALL == 1)
+      return reinterpret_cast<const void*>(&stencil_tbl_wall_src<Real, R, WY, K, Q, NTS, SW>);
+    else if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
     else if constexpr (WALL == 2) return reinterpret_cast<const void*>(&stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>);
     else if constexpr (WALL == 1) return reinterpret_cast<const void*>(&stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>);
     else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>);
   }();
   static_assert(EW == 0 || !SRC, "the edge role has no source form");
-  static_assert(!WALL || (!SRC && EW == 0), "the wall form has no source form and no edge role");
+  static_assert(!WALL || EW == 0, "the wall form has no edge role");
   HEAT3D_CHECK(SRC == (p.src != nullptr), "tl: source form mismatch");
   HEAT3D_CHECK((WALL != 0) == p.has_walls() && (WALL == 2) == p.has_convective(), "tl: wall form mismatch");
   Box b = p.box;
@@ -348,7 +375,15 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       std::fprintf(stderr, "[heat3d trace] tl K=%d box x %lld: zs=%d L=%d seg=%d tiles=%dx%d blocks=%lld (model %.1f)\n",
                    K, (long long)nxb, zs, Lx, xp.seg, ga.nzb, ga.nyb, (long long)nblocks,
                    xplan_makespan(xp, nxb, tiles, slots, 2 * (K - 1), U));
-    if constexpr (SRC)
+    if constexpr (SRC && WALL == 2)
+      hipLaunchKernelGGL((stencil_tbl_conv_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
+                         s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out),
+                         static_cast<const Real*>(p.src), ga, wl, cv, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
+    else if constexpr (SRC && WALL == 1)
+      hipLaunchKernelGGL((stencil_tbl_wall_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
+                         s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out),
+                         static_cast<const Real*>(p.src), ga, wl, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
+    else if constexpr (SRC)
       hipLaunchKernelGGL((stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
                          static_cast<const Real*>(p.in), static_cast<Real*>(p.out), static_cast<const Real*>(p.src),
                          ga, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
@@ -374,7 +409,9 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       const int wide = 64 - 2 * K, aligned = sizeof(Real) == 8 ? wide & ~7 : wide;
       for (int z : {wide, aligned})
         if (std::find(zs_opts.begin(), zs_opts.end(), z) == zs_opts.end()) zs_opts.push_back(z);
-      tune_schedule(SRC    ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src")
+      tune_schedule(SRC && WALL == 2 ? (sizeof(Real) == 8 ? "tl-fp64-conv-src" : "tl-fp32-conv-src")
+                    : SRC && WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall-src" : "tl-fp32-wall-src")
+                    : SRC    ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src")
                     : WALL == 2 ? (sizeof(Real) == 8 ? "tl-fp64-conv" : "tl-fp32-conv")
                     : WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall" : "tl-fp32-wall")
                     : sizeof(Real) == 8 ? "tl-fp64" : "tl-fp32",

@@ -10,6 +10,10 @@
 // stencil_tbl_conv, stencil_tbl_conv.hip) is the convective-wall form: the same
 // masked step, with the ghost fma(beta, T_inf - c, c) of the face (TBLConv) in
 // place of the centre value c; an insulated face enters with beta = 0.
+// H3D_TBL_SRC 1 together with H3D_TBL_WALL 1 / 2 (kernels stencil_tbl_wall_src /
+// stencil_tbl_conv_src, stencil_tbl_wall_src.hip / stencil_tbl_conv_src.hip): the
+// wall step with the source rows of the source form; the ghost substitution
+// comes first, the source is added to the finished update.
 //
 // EW > 0: the edge role (impl.hpp, third step form).  Waves 0 and WY - 1 hold
 // the tile's K halo rows and E = EW - 1 owned rows next to them (R + E rows; the
@@ -39,7 +43,7 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
   constexpr int RB = R + E;             // rows of an edge wave (register rows of every wave)
   static_assert(!EDGE || (R >= K && WY >= 3 && !SW && !H3D_TBL_SRC), "edge role: halo-only waves, no source form");
 #if H3D_TBL_WALL
-  static_assert(!EDGE && !H3D_TBL_SRC, "the wall form has no edge role and no source form");
+  static_assert(!EDGE, "the wall form has no edge role");
 #endif
   constexpr int TY = WY * R + 2 * E;
   constexpr int YS = TY - 2 * K;   // tile stride along y (stored rows)
@@ -328,8 +332,15 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         }
 #endif
         // (SW: the rows are the x terms of the update, the marching axis its y terms)
+#if H3D_TBL_SRC
+        // (the order of the single-step path: wall planes refreshed, then ftcs_update_src)
+        const Real nv = add_source<Real>(SW ? ftcs<Real>(C[r], ym, yp, xm, xp, zm, zp, Dx, Dy, Dz)
+                                            : ftcs<Real>(C[r], xm, xp, ym, yp, zm, zp, Dx, Dy, Dz),
+                                         S[r]);
+#else
         const Real nv = SW ? ftcs<Real>(C[r], ym, yp, xm, xp, zm, zp, Dx, Dy, Dz)
                            : ftcs<Real>(C[r], xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);
+#endif
 #else
         const Real ym = r == 0 ? lo : C[r > 0 ? r - 1 : 0];
         const Real yp = r == NR - 1 ? hi : C[r + 1 < NR ? r + 1 : 0];

@@ -245,6 +245,10 @@ PYBIND11_MODULE(_heat3d, m) {
   m.def("lean_wall_supported", [](const std::string& dtype, const std::string& spec) {
     return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true);
   }, py::arg("dtype"), py::arg("spec"));
+  // ... its wall form with a heat source (convective: the convective form with one)
+  m.def("lean_wall_source_supported", [](const std::string& dtype, const std::string& spec, bool convective) {
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), true, true, convective);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("convective") = false);
   m.def("lean_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
     const heat3d::KernelSpec k = heat3d::KernelSpec::parse(spec);
     if (!k.multi_step()) throw UsageError("lean_supported needs a tl2..tl6 kernel");

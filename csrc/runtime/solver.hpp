@@ -319,8 +319,11 @@ class Solver {
   // lean kernel (StencilParams::wall: the substitution happens in the kernel,
   // at every stage).  Single steps run the kernels as they are on wall planes
   // refreshed from their inward neighbours (refresh_walls), which gives the
-  // same bits.  With a source or a conductivity as well there is no sweep
-  // form: every iteration is such a single step (walls_single).
+  // same bits.  With a conductivity as well there is no sweep form: every
+  // iteration is such a single step (walls_single).  With a source there is
+  // one (the wall forms with a source, stencil_tbl_wall_src.hip and
+  // stencil_tbl_conv_src.hip), used where Config::wall_source_sweeps asks for
+  // it; by default a source with walls runs as single steps too.
   // Convective walls (Config::convective, ambient) are walls in all of this:
   // walls_ holds the insulated and the convective faces, conv_ the convective
   // ones with their coefficients in conv_beta_.  Their sweeps run the
@@ -329,7 +332,7 @@ class Solver {
   // the wall plane with the ghost values (Backend::refresh_convective).
   unsigned walls_ = 0, conv_ = 0;
   double conv_beta_[6] = {-1, -1, -1, -1, -1, -1};
-  bool walls_single() const { return walls_ && (has_source_ || has_cond_); }
+  bool walls_single() const { return walls_ && (has_cond_ || (has_source_ && !cfg_.wall_source_sweeps)); }
   void set_walls(StencilParams& sp, const Local& l) const;
   // wall planes of buffer b <- their inward neighbours, axis order x, y, z,
   // over the whole local extent of the other axes (ghosts included); vertices

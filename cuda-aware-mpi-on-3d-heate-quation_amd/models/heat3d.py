@@ -153,6 +153,30 @@ class HeatEquation3D:
         v[-1] = 1.0
         return np.broadcast_to(v[None, :, None], self.n).copy()
 
+    def convective_slab_source_steady(self, beta: float, ambient: float, q: float) -> np.ndarray:
+        """Exact steady state of the discrete scheme for the slab problem of
+        ``convective_slab_steady`` with a uniform heat source ``q``.  With
+        sigma = dt q / D_y and M = Ny - 2, T_j = A + B j - sigma j^2 / 2 on
+        j = 1 .. M, where A and B solve
+        beta A = (1 - beta) (B - sigma / 2) + beta T_inf (the y- wall) and
+        A + B (M + 1) - sigma (M + 1)^2 / 2 = 1 (y+ Dirichlet at 1).  Constant in
+        x and z; the y- wall vertices hold the ghost T_1 + beta (T_inf - T_1), y+
+        holds 1 (global array)."""
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"convective_slab_source_steady: beta {beta} outside (0, 1]")
+        Ny = self.n[1]
+        M = Ny - 2
+        sigma = self.dt * float(q) / self.D[1]
+        # A = ((1 - beta) (B - sigma / 2) + beta T_inf) / beta in the y+ condition
+        r = (1.0 - beta) / beta
+        B = (1.0 + sigma * (M + 1) ** 2 / 2.0 + r * sigma / 2.0 - ambient) / (r + M + 1)
+        A = r * (B - sigma / 2.0) + ambient
+        j = np.arange(Ny, dtype=np.float64)
+        v = A + B * j - sigma * j * j / 2.0
+        v[0] = v[1] + beta * (ambient - v[1])
+        v[-1] = 1.0
+        return np.broadcast_to(v[None, :, None], self.n).copy()
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -180,7 +204,7 @@ class HeatSolver:
                  check_every: int = 64, graph_chunk: int = 0, device: Optional[int] = None,
                  threads: int = 0, extra_args: Sequence[str] = (), group=None,
                  phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False,
-                 insulated=None, convective=None, ambient: float = 0.0):
+                 insulated=None, convective=None, ambient: float = 0.0, wall_source_sweeps: bool = False):
         ext = native()
         self.model = HeatEquation3D(tuple(int(v) for v in n))  # type: ignore[arg-type]
         args: List[str] = [str(int(v)) for v in n] + [str(int(iter_max)), _fmt(eps)]
@@ -201,6 +225,9 @@ class HeatSolver:
         if conductivity_sweeps:
             # with a conductivity field: K-step sweeps of the tv kernels instead of single steps
             args.append("--conductivity-sweeps")
+        if wall_source_sweeps:
+            # with insulated / convective walls and a heat source: K-step sweeps instead of single steps
+            args.append("--wall-source-sweeps")
         if insulated:
             # zero-flux walls: names of x-, x+, y-, y+, z-, z+ (a sequence or a comma list) or "all";
             # the native parser validates them (UsageError)

@@ -158,8 +158,8 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
 
     ``walls``: insulated walls as ``wall_coords`` gives them (CPU tensors only,
-    without source / conductivity: the single-step gfx950 kernels run on wall
-    planes copied from their inward neighbours instead).  ``conv``: the faces
+    with or without a source, not with a conductivity: the single-step gfx950
+    kernels run on wall planes copied from their inward neighbours instead).  ``conv``: the faces
     among them that are convective (``convective_faces`` forms), with the
     ambient temperature ``ambient``.
 
@@ -269,7 +269,10 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     kernel (stencil_tbl_wall.hip; a spec without one is a RuntimeError).
     ``conv``: the faces among ``walls`` that are convective (``convective_faces``
     forms: the coefficient per face) with the ambient temperature ``ambient``;
-    GPU tensors then run the convective form (stencil_tbl_conv.hip)."""
+    GPU tensors then run the convective form (stencil_tbl_conv.hip).  ``walls``
+    together with ``source``: the wall or convective form with a source
+    (stencil_tbl_wall_src.hip / stencil_tbl_conv_src.hip) on GPU tensors, K
+    single steps with both on CPU tensors."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
