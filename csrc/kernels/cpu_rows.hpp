@@ -7,127 +7,73 @@
 // x86-64 and once with -mfma -mavx2 (cpu_rows_fma.cpp); cpu_row_kernels()
 // picks the FMA build when the running CPU has FMA + AVX2.  Both builds give
 // bitwise identical results.
+//
+// One row template covers the forms of the uniform update (kernels.hpp
+// SweepForm: with or without a heat source, behind no, insulated or convective
+// walls), a second one the update with a conductivity field.  Every row has
+// the same signature, and each build exports one table of them.
 #pragma once
 
 #include <cstdint>
 
+#include "kernels.hpp"
+
 namespace heat3d {
 namespace cpu {
 
-// out[k] = ftcs_update(in[k], ...) for k in [0, n); returns max |out - in|
-// (NaN-propagating, as a double).
+// One row: out[k] = the update of in[k] for k in [0, n).  A form reads the
+// fields that concern it and ignores the others.
 template <typename Real>
-using FtcsRowFn = double (*)(const Real* in, Real* out, int64_t n, int64_t sx, int64_t sy, Real Dx, Real Dy,
-                             Real Dz);
-
-// the same with a heat source: out[k] = ftcs_update_src(in[k], ..., src[k])
-template <typename Real>
-using FtcsRowSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t sx, int64_t sy,
-                                Real Dx, Real Dy, Real Dz);
-
-// with a conductivity field: out[k] = ftcs_update_var(in[k], ..., cond[k], ...),
-// plus src[k] where src != nullptr (ftcs_update_var_src)
-template <typename Real>
-using FtcsRowVarFn = double (*)(const Real* in, Real* out, const Real* cond, const Real* src, int64_t n, int64_t sx,
-                                int64_t sy, Real Dx, Real Dy, Real Dz);
-
-// insulated walls (StencilParams::wall): om / op are the offsets of the x and
-// y neighbours (0 where the neighbour across a wall is replaced by the centre
-// value), kzm / kzp the row indices whose z- / z+ neighbour is (-1: none)
-template <typename Real>
-using FtcsRowWallFn = double (*)(const Real* in, Real* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym,
-                                 int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz);
-
-// convective walls (StencilParams::wall_beta): as FtcsRowWallFn, with the
-// coefficients of the six faces (x-, x+, y-, y+, z-, z+; 0 on an insulated one)
-// and the ambient temperature
-template <typename Real>
-using FtcsRowConvFn = double (*)(const Real* in, Real* out, int64_t n, int64_t oxm, int64_t oxp, int64_t oym,
-                                 int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf, Real Dx, Real Dy,
-                                 Real Dz);
-
-// walls with a heat source: FtcsRowWallFn / FtcsRowConvFn with src[k] added to
-// the finished update (ftcs_update_src; the ghost substitution comes first)
-template <typename Real>
-using FtcsRowWallSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t oxm, int64_t oxp,
-                                    int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, Real Dx, Real Dy, Real Dz);
-template <typename Real>
-using FtcsRowConvSrcFn = double (*)(const Real* in, Real* out, const Real* src, int64_t n, int64_t oxm, int64_t oxp,
-                                    int64_t oym, int64_t oyp, int64_t kzm, int64_t kzp, const Real* beta, Real tinf,
-                                    Real Dx, Real Dy, Real Dz);
-
-struct RowKernels {
-  FtcsRowFn<double> f64;
-  FtcsRowFn<float> f32;
-  const char* isa;
-  FtcsRowSrcFn<double> src_f64;
-  FtcsRowSrcFn<float> src_f32;
-  FtcsRowVarFn<double> var_f64;
-  FtcsRowVarFn<float> var_f32;
-  FtcsRowWallFn<double> wall_f64;
-  FtcsRowWallFn<float> wall_f32;
-  FtcsRowConvFn<double> conv_f64;
-  FtcsRowConvFn<float> conv_f32;
-  FtcsRowWallSrcFn<double> wall_src_f64;
-  FtcsRowWallSrcFn<float> wall_src_f32;
-  FtcsRowConvSrcFn<double> conv_src_f64;
-  FtcsRowConvSrcFn<float> conv_src_f32;
+struct RowArgs {
+  const Real* in;
+  Real* out;
+  int64_t n;
+  Real Dx, Dy, Dz;
+  const Real* src;   // heat source: src[k] is added to the finished update (ftcs_update_src)
+  const Real* cond;  // conductivity form (ftcs_update_var; with src != nullptr ftcs_update_var_src)
+  int64_t sx, sy;    // strides of the x and y neighbours (the forms without walls)
+  // walls (StencilParams::wall): the offsets of the x and y neighbours, 0 where
+  // the neighbour across a wall is replaced by the ghost value, and the row
+  // indices whose z- / z+ neighbour is (-1 or beyond n: none).  The ghost is
+  // the centre value behind insulated walls, convective_ghost(T, beta, tinf)
+  // behind convective ones (the ghost substitution comes first, then the source)
+  int64_t oxm, oxp, oym, oyp, kzm, kzp;
+  // convective walls (StencilParams::wall_beta): the coefficients of the six
+  // faces (x-, x+, y-, y+, z-, z+; 0 on an insulated one), the ambient temperature
+  const Real* beta;
+  Real tinf;
 };
 
+// returns max |out - in| over the row (NaN-propagating, as a double)
+template <typename Real>
+using RowFn = double (*)(const RowArgs<Real>&);
+
+template <typename Real>
+struct RowTable {
+  RowFn<Real> row[2][3];  // [SweepForm::src][SweepForm::wall]
+  RowFn<Real> var;        // the conductivity form
+};
+
+struct RowKernels {
+  RowTable<double> f64;
+  RowTable<float> f32;
+  const char* isa;
+  template <typename Real>
+  const RowTable<Real>& of() const {
+    if constexpr (sizeof(Real) == 8) return f64;
+    else return f32;
+  }
+};
+
+// the table of the build this CPU runs
 const RowKernels& cpu_row_kernels();
 
 namespace rows_generic {
-double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
-double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
-double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
-double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
-double ftcs_row_var_f64(const double*, double*, const double*, const double*, int64_t, int64_t, int64_t, double,
-                        double, double);
-double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
-                        float);
-double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double,
-                         double, double);
-double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
-                         float, float);
-double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                         const double*, double, double, double, double);
-double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                         const float*, float, float, float, float);
-double ftcs_row_wall_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, double, double, double);
-double ftcs_row_wall_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, float, float, float);
-double ftcs_row_conv_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, const double*, double, double, double, double);
-double ftcs_row_conv_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, const float*, float, float, float, float);
-}  // namespace rows_generic
+extern const RowKernels table;
+}
 namespace rows_fma {
-double ftcs_row_f64(const double*, double*, int64_t, int64_t, int64_t, double, double, double);
-double ftcs_row_f32(const float*, float*, int64_t, int64_t, int64_t, float, float, float);
-double ftcs_row_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, double, double, double);
-double ftcs_row_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, float, float, float);
-double ftcs_row_var_f64(const double*, double*, const double*, const double*, int64_t, int64_t, int64_t, double,
-                        double, double);
-double ftcs_row_var_f32(const float*, float*, const float*, const float*, int64_t, int64_t, int64_t, float, float,
-                        float);
-double ftcs_row_wall_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, double,
-                         double, double);
-double ftcs_row_wall_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, float,
-                         float, float);
-double ftcs_row_conv_f64(const double*, double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                         const double*, double, double, double, double);
-double ftcs_row_conv_f32(const float*, float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                         const float*, float, float, float, float);
-double ftcs_row_wall_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, double, double, double);
-double ftcs_row_wall_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, float, float, float);
-double ftcs_row_conv_src_f64(const double*, double*, const double*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, const double*, double, double, double, double);
-double ftcs_row_conv_src_f32(const float*, float*, const float*, int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, const float*, float, float, float, float);
-}  // namespace rows_fma
+extern const RowKernels table;
+}
 
 }  // namespace cpu
 }  // namespace heat3d

@@ -48,6 +48,16 @@ struct KernelSpec {
 // StencilParams::wall: no insulated wall on this side
 constexpr int64_t kNoWall = -(int64_t(1) << 40);
 
+// Which form of the uniform update a call asks for: with a heat source or
+// without, and behind which kind of wall (Convective as soon as one face is;
+// the values are the lean kernels' WALL template argument).  Derived once, by
+// StencilParams::form(); the CPU rows and the lean sweep's dispatch select by it.
+enum class WallKind { None = 0, Insulated = 1, Convective = 2 };
+struct SweepForm {
+  bool src = false;
+  WallKind wall = WallKind::None;
+};
+
 struct StencilParams {
   const void* in = nullptr;
   void* out = nullptr;
@@ -104,11 +114,6 @@ struct StencilParams {
   // (stencil_tbl_wall.hip; with a source stencil_tbl_wall_src.hip); the
   // single-step gfx950 kernels do not take it.
   int64_t wall[3][2] = {{kNoWall, kNoWall}, {kNoWall, kNoWall}, {kNoWall, kNoWall}};
-  bool has_walls() const {
-    for (int a = 0; a < 3; ++a)
-      if (wall[a][0] != kNoWall || wall[a][1] != kNoWall) return true;
-    return false;
-  }
   // Convective (Robin) walls, -k dT/dn = h (T - T_inf): a face with a wall
   // coordinate above and wall_beta[a][e] >= 0 is convective with that
   // coefficient (0 <= beta <= 1; negative: the face is insulated or has no
@@ -121,12 +126,19 @@ struct StencilParams {
   // stencil_tbl_conv_src.hip).
   double wall_beta[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
   double ambient = 0;
-  bool has_convective() const {
+  // the one place that reads src, wall and wall_beta for the form of the call
+  SweepForm form() const {
+    SweepForm f;
+    f.src = src != nullptr;
     for (int a = 0; a < 3; ++a)
       for (int e = 0; e < 2; ++e)
-        if (wall[a][e] != kNoWall && wall_beta[a][e] >= 0) return true;
-    return false;
+        if (wall[a][e] != kNoWall) {
+          if (wall_beta[a][e] >= 0) f.wall = WallKind::Convective;
+          else if (f.wall == WallKind::None) f.wall = WallKind::Insulated;
+        }
+    return f;
   }
+  bool has_walls() const { return form().wall != WallKind::None; }
 };
 
 struct InitParams {
@@ -190,20 +202,33 @@ void stencil_lean_pair(DType t, const StencilParams& p, const KernelSpec& k, voi
 bool lean_pair_supported(DType t, const KernelSpec& k);
 // z tile stride of the pair kernel for a box (host-side choice, stencil_tbp.hip)
 int pair_z_stride(int64_t nx, int64_t ny, int64_t nz, int K, int TY, int slots, int U, int L, int esize);
-// Is the lean kernel variant that k resolves to for dtype t instantiated?
-// with_source: its heat-source form (StencilParams::src != nullptr)
-// with_walls: its insulated-wall form (StencilParams::has_walls)
-// with_convective: its convective-wall form (StencilParams::has_convective; implies walls)
-// with_source and walls: the wall or convective form with a source
-bool lean_supported(DType t, const KernelSpec& k, bool with_source = false, bool with_walls = false,
-                    bool with_convective = false);
-// the wall forms' dispatch (stencil_tbl_wall.hip); p == nullptr: only report
-bool lean_wall_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
-// the convective forms' (stencil_tbl_conv.hip)
-bool lean_conv_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
-// the same two with a heat source (stencil_tbl_wall_src.hip, stencil_tbl_conv_src.hip)
-bool lean_wall_src_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
-bool lean_conv_src_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream);
+// Is the lean kernel variant that k resolves to for dtype t instantiated in
+// the given form (StencilParams::form)?
+bool lean_supported(DType t, const KernelSpec& k, SweepForm form = {});
+// The tile of a lean launch: R rows per wave, WY waves, SW the y-marching form
+struct LeanShape {
+  int R = 0, WY = 0;
+  bool SW = false;
+};
+// The thin-slab rule of every lean dispatch: a box of few x planes and long
+// rows (the boundary slabs of x-slab decompositions) under a default spec (no
+// V, R, WY, Q field) runs as y-marching tiles of WY waves x R x-rows: 5 x 2 for
+// the 4-plane slabs of a K = 3 sweep, 3 x 3 for its other slabs of up to 2K
+// planes, 4 x 3 for slabs of up to K = 4 planes.  false: the x-marching tile.
+inline bool lean_thin_slab(int K, bool default_spec, int64_t extent_x, int64_t extent_y, LeanShape* shape) {
+  if (!default_spec || extent_x <= 0 || extent_y < 16 * extent_x) return false;
+  if (K == 3 && extent_x == 4) *shape = {2, 5, true};
+  else if (K == 3 && extent_x <= 2 * K) *shape = {3, 3, true};
+  else if (K == 4 && extent_x <= K) *shape = {3, 4, true};
+  else return false;
+  return true;
+}
+// The lean sweep's dispatch of any form: launches *p with the variant k
+// resolves to, or (p == nullptr) only reports whether that variant exists;
+// either way *shape, if given, receives the tile that runs (unchanged for the
+// packed-pair kernel of stencil_tbp.hip, which has no such tile).
+bool lean_dispatch(DType t, SweepForm form, const StencilParams* p, const KernelSpec& k, void* stream,
+                   LeanShape* shape = nullptr);
 // Convective walls on single steps: dst box (one wall plane) <- the ghost value
 // convective_ghost of the src box (the first interior plane), same field
 void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,

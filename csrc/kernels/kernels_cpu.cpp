@@ -70,73 +70,40 @@ static void stencil_t(const StencilParams& p) {
   // max |dT| reduced on the IEEE bit patterns of the non-negative doubles so
   // that a NaN (bits above +Inf) propagates to the convergence check
   unsigned long long resbits = 0;
-  const auto rowfn = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().f64;
-    else return cpu_row_kernels().f32;
-  }();
-  const auto rowsrc = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().src_f64;
-    else return cpu_row_kernels().src_f32;
-  }();
-  const auto rowvar = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().var_f64;
-    else return cpu_row_kernels().var_f32;
-  }();
-  const auto rowwall = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().wall_f64;
-    else return cpu_row_kernels().wall_f32;
-  }();
-  const auto rowconv = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().conv_f64;
-    else return cpu_row_kernels().conv_f32;
-  }();
-  const auto rowwallsrc = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().wall_src_f64;
-    else return cpu_row_kernels().wall_src_f32;
-  }();
-  const auto rowconvsrc = [] {
-    if constexpr (sizeof(Real) == 8) return cpu_row_kernels().conv_src_f64;
-    else return cpu_row_kernels().conv_src_f32;
-  }();
-  // convective walls (StencilParams::wall_beta): the coefficients in the
-  // field's dtype, 0 on the insulated faces of the same call
-  const bool conv = p.has_convective();
-  Real beta[6];
-  for (int f = 0; f < 6; ++f) beta[f] = static_cast<Real>(p.wall_beta[f / 2][f % 2] > 0 ? p.wall_beta[f / 2][f % 2] : 0);
-  const Real tinf = static_cast<Real>(p.ambient);
-  // insulated walls (StencilParams::wall): the uniform update, with or without a source
-  const bool walls = p.has_walls();
-  HEAT3D_CHECK(!walls || !p.cond,
+  // the row of the call's form (cpu_rows.hpp): one lookup, one call per row
+  const SweepForm form = p.form();
+  HEAT3D_CHECK(form.wall == WallKind::None || !p.cond,
                "cpu::stencil: insulated / convective walls with a conductivity run as single steps on copied wall "
                "planes, not through StencilParams::wall");
-  const Real* __restrict src = static_cast<const Real*>(p.src);  // heat source S, or nullptr
-  const Real* __restrict cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
-  const int64_t nk = b.extent(2);
+  const RowTable<Real>& rows = cpu_row_kernels().of<Real>();
+  const RowFn<Real> rowfn = p.cond ? rows.var : rows.row[form.src][(int)form.wall];
+  // convective walls (StencilParams::wall_beta): the coefficients in the
+  // field's dtype, 0 on the insulated faces of the same call
+  Real beta[6];
+  for (int f = 0; f < 6; ++f) beta[f] = static_cast<Real>(p.wall_beta[f / 2][f % 2] > 0 ? p.wall_beta[f / 2][f % 2] : 0);
+  const Real* src = static_cast<const Real*>(p.src);    // heat source S, or nullptr
+  const Real* cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
+  RowArgs<Real> row{};
+  row.n = b.extent(2);
+  row.Dx = Dx, row.Dy = Dy, row.Dz = Dz;
+  row.sx = sx, row.sy = sy;
+  row.kzm = p.wall[2][0] - b.lo[2], row.kzp = p.wall[2][1] - b.lo[2];
+  row.beta = beta;
+  row.tinf = static_cast<Real>(p.ambient);
 #pragma omp parallel for collapse(2) schedule(static) reduction(max : resbits) if (omp_worth(b.volume()))
   for (int64_t i = b.lo[0]; i < b.hi[0]; ++i)
     for (int64_t j = b.lo[1]; j < b.hi[1]; ++j) {
       const int64_t c = L.index(i, j, b.lo[2]);
+      RowArgs<Real> a = row;
+      a.in = in + c;
+      a.out = out + c;
+      a.src = src ? src + c : nullptr;
+      a.cond = cond ? cond + c : nullptr;
+      // insulated / convective walls (StencilParams::wall): offset 0 where the neighbour is the ghost
+      a.oxm = i == p.wall[0][0] ? 0 : -sx, a.oxp = i == p.wall[0][1] ? 0 : sx;
+      a.oym = j == p.wall[1][0] ? 0 : -sy, a.oyp = j == p.wall[1][1] ? 0 : sy;
       // heat3D.cu:128-131 with nvcc's FMA contraction (kernels.hpp ftcs_update)
-      const double lres = nk <= 0 ? 0.0
-                          : conv && src
-                              ? rowconvsrc(in + c, out + c, src + c, nk, i == p.wall[0][0] ? 0 : -sx,
-                                           i == p.wall[0][1] ? 0 : sx, j == p.wall[1][0] ? 0 : -sy,
-                                           j == p.wall[1][1] ? 0 : sy, p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2],
-                                           beta, tinf, Dx, Dy, Dz)
-                          : walls && src
-                              ? rowwallsrc(in + c, out + c, src + c, nk, i == p.wall[0][0] ? 0 : -sx,
-                                           i == p.wall[0][1] ? 0 : sx, j == p.wall[1][0] ? 0 : -sy,
-                                           j == p.wall[1][1] ? 0 : sy, p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2],
-                                           Dx, Dy, Dz)
-                          : conv  ? rowconv(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
-                                            j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
-                                            p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], beta, tinf, Dx, Dy, Dz)
-                          : walls ? rowwall(in + c, out + c, nk, i == p.wall[0][0] ? 0 : -sx, i == p.wall[0][1] ? 0 : sx,
-                                            j == p.wall[1][0] ? 0 : -sy, j == p.wall[1][1] ? 0 : sy,
-                                            p.wall[2][0] - b.lo[2], p.wall[2][1] - b.lo[2], Dx, Dy, Dz)
-                          : cond  ? rowvar(in + c, out + c, cond + c, src ? src + c : nullptr, nk, sx, sy, Dx, Dy, Dz)
-                          : src   ? rowsrc(in + c, out + c, src + c, nk, sx, sy, Dx, Dy, Dz)
-                                  : rowfn(in + c, out + c, nk, sx, sy, Dx, Dy, Dz);
+      const double lres = a.n <= 0 ? 0.0 : rowfn(a);
       unsigned long long bits;
       std::memcpy(&bits, &lres, sizeof(bits));
       resbits = bits > resbits ? bits : resbits;

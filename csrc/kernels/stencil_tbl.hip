@@ -3,7 +3,7 @@
 // and its launcher live in stencil_tbl_impl.hpp; the variants (listed in
 // stencil_tbl_variants.inc) are instantiated by the stencil_tbl_part*.hip
 // units so that they compile in parallel.
-#include "stencil_tbl_impl.hpp"
+#include "stencil_tbl_form.hpp"
 
 #include <array>
 #include <map>
@@ -78,22 +78,13 @@ static bool dispatch_tbl_src(const StencilParams* p, const KernelSpec& k, hipStr
   if (k1.V == 0) k1.V = 1;
   const KernelSpec r = k1.resolved(f64 ? DType::F64 : DType::F32);
   const int K = k.K, R = r.R, WY = r.WY, Q = r.NT;
-  if (p) {
-    // the thin x slabs' y-marching tiles, chosen as dispatch_tbl chooses them
-    const Box& bx = p->box;
-    const bool dflt = k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0;
-    if (K == 3 && dflt && bx.extent(0) == 4 && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 2, 5, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
-      return true;
-    }
-    if (K == 3 && dflt && bx.extent(0) > 0 && bx.extent(0) <= 2 * K && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 3, 3, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
-      return true;
-    }
-    if (K == 4 && dflt && bx.extent(0) > 0 && bx.extent(0) <= K && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 3, 4, 4, 3, f64 ? 2 : 0, true, true>(*p, k, s);
-      return true;
-    }
+  // the thin x slabs' y-marching tiles, chosen as dispatch_tbl chooses them
+  LeanShape thin;
+  if (p && lean_thin_slab(K, k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0, p->box.extent(0), p->box.extent(1), &thin)) {
+    if (thin.WY == 5) launch_tbl<Real, 2, 5, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+    else if (thin.WY == 3) launch_tbl<Real, 3, 3, 3, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+    else launch_tbl<Real, 3, 4, 4, 3, f64 ? 2 : 0, true, true>(*p, k, s);
+    return true;
   }
   if (r.V != 1 || r.WZ != 1 || Q != 3 || r.EW != 0) return false;  // (the edge role has no source form)
   const int O = r.O > 0 ? r.O : 0;
@@ -124,30 +115,18 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   // 4-plane pipeline fill along x.  Phantom rank of the 1024^3 fp64 slab
   // bench (64 GB/s emulated links): 8 ranks 0.2135 -> 0.2084 ms per step, 4
   // ranks 0.379 -> 0.359, 2 ranks unchanged (profiles/boundary_slabs_r02.md).
-  if (p) {
-    const Box& bx = p->box;
-    // 4-plane slabs of a K = 3 sweep before a long sweep (Solver::enqueue_multi
-    // thick): 5-wave tiles of 10 x-rows store all 4 planes in one tile
-    if (K == 3 && k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0 && bx.extent(0) == 4 &&
-        bx.extent(1) >= 16 * bx.extent(0)) {
-      if constexpr (sizeof(Real) == 8) launch_tbl<Real, 2, 5, 3, 3, 2, true>(*p, k, s);
-      else launch_tbl<Real, 2, 5, 3, 3, 0, true>(*p, k, s);
-      return true;
-    }
-    if (K == 3 && k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0 && bx.extent(0) > 0 && bx.extent(0) <= 2 * K &&
-        bx.extent(1) >= 16 * bx.extent(0)) {
-      if constexpr (sizeof(Real) == 8) launch_tbl<Real, 3, 3, 3, 3, 2, true>(*p, k, s);
-      else launch_tbl<Real, 3, 3, 3, 3, 0, true>(*p, k, s);
-      return true;
-    }
-    // the (K+1)-plane boundary slabs of long sweeps across x halos (K = 4):
-    // 4-wave tiles of 12 x-rows store the 4 slab planes
-    if (K == 4 && k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0 && bx.extent(0) > 0 && bx.extent(0) <= K &&
-        bx.extent(1) >= 16 * bx.extent(0)) {
-      if constexpr (sizeof(Real) == 8) launch_tbl<Real, 3, 4, 4, 3, 2, true>(*p, k, s);
-      else launch_tbl<Real, 3, 4, 4, 3, 0, true>(*p, k, s);
-      return true;
-    }
+  // (kernels.hpp lean_thin_slab is the rule.)  4-plane slabs of a K = 3 sweep
+  // before a long sweep (Solver::enqueue_multi thick): 5-wave tiles of 10 x-rows
+  // store all 4 planes in one tile; the (K+1)-plane boundary slabs of long
+  // sweeps across x halos (K = 4): 4-wave tiles of 12 x-rows store the 4 slab
+  // planes
+  LeanShape thin;
+  if (p && lean_thin_slab(K, k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0, p->box.extent(0), p->box.extent(1), &thin)) {
+    constexpr int nts = sizeof(Real) == 8 ? 2 : 0;
+    if (thin.WY == 5) launch_tbl<Real, 2, 5, 3, 3, nts, true>(*p, k, s);
+    else if (thin.WY == 3) launch_tbl<Real, 3, 3, 3, 3, nts, true>(*p, k, s);
+    else launch_tbl<Real, 3, 4, 4, 3, nts, true>(*p, k, s);
+    return true;
   }
   if (r.V == 2) {  // two columns per lane: packed fp32 / 16-byte fp64 pairs (stencil_tbp.hip)
     if (r.EW != 0) return false;  // (no edge role there)
@@ -220,55 +199,61 @@ static bool dispatch_tbl(const StencilParams* p, const KernelSpec& k, hipStream_
   return false;
 }
 
-bool lean_supported(DType t, const KernelSpec& k, bool with_source, bool with_walls, bool with_convective) {
-  // (walls with a source: forms of their own, stencil_tbl_wall_src.hip / stencil_tbl_conv_src.hip)
-  if (with_convective)
-    return k.kind == KernelSpec::TBL && (with_source ? lean_conv_src_dispatch(t, nullptr, k, nullptr)
-                                                     : lean_conv_dispatch(t, nullptr, k, nullptr));
-  if (with_walls)
-    return k.kind == KernelSpec::TBL && (with_source ? lean_wall_src_dispatch(t, nullptr, k, nullptr)
-                                                     : lean_wall_dispatch(t, nullptr, k, nullptr));
-  if (with_source)
-    return t == DType::F64 ? dispatch_tbl_src<double>(nullptr, k, nullptr) : dispatch_tbl_src<float>(nullptr, k, nullptr);
-  return t == DType::F64 ? dispatch_tbl<double>(nullptr, k, nullptr) : dispatch_tbl<float>(nullptr, k, nullptr);
+// The forms without walls are the two dispatch functions above.  Their tile is
+// the thin-slab one or the one the spec resolves to, never another (the pair
+// kernel reports none).
+static void unwalled_shape(DType t, KernelSpec k, bool src, const StencilParams* p, LeanShape* shape) {
+  if (p && lean_thin_slab(k.K, k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0, p->box.extent(0), p->box.extent(1), shape))
+    return;
+  if (src && k.V == 0) k.V = 1;
+  const KernelSpec r = k.resolved(t);
+  if (r.V == 1) *shape = LeanShape{r.R, r.WY, false};
+}
+template <>
+bool lean_form_dispatch<false, 0>(DType t, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape) {
+  const bool ok = t == DType::F64 ? dispatch_tbl<double>(p, k, s) : dispatch_tbl<float>(p, k, s);
+  if (ok && shape) unwalled_shape(t, k, false, p, shape);
+  return ok;
+}
+template <>
+bool lean_form_dispatch<true, 0>(DType t, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape) {
+  const bool ok = t == DType::F64 ? dispatch_tbl_src<double>(p, k, s) : dispatch_tbl_src<float>(p, k, s);
+  if (ok && shape) unwalled_shape(t, k, true, p, shape);
+  return ok;
+}
+
+bool lean_dispatch(DType t, SweepForm form, const StencilParams* p, const KernelSpec& k, void* stream, LeanShape* shape) {
+  using Fn = bool (*)(DType, const StencilParams*, const KernelSpec&, hipStream_t, LeanShape*);
+  static constexpr Fn forms[2][3] = {  // [src][wall]
+      {lean_form_dispatch<false, 0>, lean_form_dispatch<false, 1>, lean_form_dispatch<false, 2>},
+      {lean_form_dispatch<true, 0>, lean_form_dispatch<true, 1>, lean_form_dispatch<true, 2>}};
+  return forms[form.src][(int)form.wall](t, p, k, S(stream), shape);
+}
+
+bool lean_supported(DType t, const KernelSpec& k, SweepForm form) {
+  return (form.wall == WallKind::None || k.kind == KernelSpec::TBL) && lean_dispatch(t, form, nullptr, k, nullptr);
 }
 
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   refuse_conductivity(p, k);
   if (p.box.empty()) return;
-  if (p.has_walls()) {
-    // a sweep next to an insulated wall never falls back to Dirichlet arithmetic
-    // (nor, next to a convective one, to insulated arithmetic)
-    const bool conv = p.has_convective();
-    const bool ok = p.src ? (conv ? lean_conv_src_dispatch(t, &p, k, stream) : lean_wall_src_dispatch(t, &p, k, stream))
-                          : (conv ? lean_conv_dispatch(t, &p, k, stream) : lean_wall_dispatch(t, &p, k, stream));
-    if (!ok) {
-      const KernelSpec r = k.resolved(t);
-      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t) << ") has no "
-                                        << (conv ? "convective-wall" : "insulated-wall") << " form"
-                                        << (p.src ? " with a heat source" : "")
-                                        << "; with insulated or convective walls use the default --kernel2 (tl2, tl3 or tl4 "
-                                           "without shape fields)");
-    }
-    return;
-  }
-  if (p.src) {
-    const bool ok =
-        t == DType::F64 ? dispatch_tbl_src<double>(&p, k, S(stream)) : dispatch_tbl_src<float>(&p, k, S(stream));
-    if (!ok) {
-      const KernelSpec r = k.resolved(t);
-      HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t)
-                                        << ") has no heat-source form; with a source use the default --kernel2 "
-                                           "(tl2, tl3 or tl4 without shape fields)");
-    }
-    return;
-  }
-  const bool ok = t == DType::F64 ? dispatch_tbl<double>(&p, k, S(stream)) : dispatch_tbl<float>(&p, k, S(stream));
-  if (!ok) {
-    const KernelSpec r = k.resolved(t);
-    HEAT3D_THROW("unsupported tl kernel variant V=" << r.V << " R=" << r.R << " WY=" << r.WY << " K=" << k.K
-                                                    << " Q=" << r.NT);
-  }
+  const SweepForm form = p.form();
+  if (lean_dispatch(t, form, &p, k, stream)) return;
+  const KernelSpec r = k.resolved(t);
+  // a sweep next to an insulated wall never falls back to Dirichlet arithmetic
+  // (nor, next to a convective one, to insulated arithmetic)
+  if (form.wall != WallKind::None)
+    HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t) << ") has no "
+                                      << (form.wall == WallKind::Convective ? "convective-wall" : "insulated-wall")
+                                      << " form" << (form.src ? " with a heat source" : "")
+                                      << "; with insulated or convective walls use the default --kernel2 (tl2, tl3 or tl4 "
+                                         "without shape fields)");
+  if (form.src)
+    HEAT3D_THROW("tl kernel variant " << r.str() << " (" << dtype_name(t)
+                                      << ") has no heat-source form; with a source use the default --kernel2 "
+                                         "(tl2, tl3 or tl4 without shape fields)");
+  HEAT3D_THROW("unsupported tl kernel variant V=" << r.V << " R=" << r.R << " WY=" << r.WY << " K=" << k.K
+                                                  << " Q=" << r.NT);
 }
 
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {

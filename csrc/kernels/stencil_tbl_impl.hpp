@@ -60,6 +60,7 @@
 #include <map>
 #include <mutex>
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 #include "hip_helpers.hpp"
@@ -233,6 +234,29 @@ __device__ __forceinline__ void static_for(Fn&& fn) {
 #undef H3D_TBL_SRC
 #undef H3D_TBL_WALL
 
+// The kernel of form (SRC, WALL), one of the six inclusions above, and the
+// name its timed schedules are stored under.  (if constexpr: only the form that
+// is asked for gets instantiated.)
+template <typename Real, int R, int WY, int K, int Q, int NTS, bool SW, bool SRC, int EW, int WALL>
+constexpr auto tbl_kernel() {
+  if constexpr (SRC && WALL == 2) return &stencil_tbl_conv_src<Real, R, WY, K, Q, NTS, SW>;
+  else if constexpr (SRC && WALL == 1) return &stencil_tbl_wall_src<Real, R, WY, K, Q, NTS, SW>;
+  else if constexpr (SRC) return &stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>;
+  else if constexpr (WALL == 2) return &stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>;
+  else if constexpr (WALL == 1) return &stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>;
+  else return &stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>;
+}
+template <typename Real, bool SRC, int WALL>
+constexpr const char* tbl_tuning_name() {
+  constexpr bool f64 = sizeof(Real) == 8;
+  if constexpr (SRC && WALL == 2) return f64 ? "tl-fp64-conv-src" : "tl-fp32-conv-src";
+  else if constexpr (SRC && WALL == 1) return f64 ? "tl-fp64-wall-src" : "tl-fp32-wall-src";
+  else if constexpr (SRC) return f64 ? "tl-fp64-src" : "tl-fp32-src";
+  else if constexpr (WALL == 2) return f64 ? "tl-fp64-conv" : "tl-fp32-conv";
+  else if constexpr (WALL == 1) return f64 ? "tl-fp64-wall" : "tl-fp32-wall";
+  else return f64 ? "tl-fp64" : "tl-fp32";
+}
+
 // EW: the edge role of waves 0 and WY - 1 (0 = off, else 1 + their owned rows)
 // WALL: 1 the insulated-wall form (p.wall; no edge role), 2 the convective-wall
 // form (p.wall_beta, p.ambient as well); either with SRC: their source forms
@@ -240,21 +264,13 @@ template <typename Real, int R, int WY, int K, int Q, int NTS = 0, bool SW = fal
           int WALL = 0>
 void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
   constexpr bool swap_xy = SW;
-  // (if constexpr: only the form that is launched gets instantiated)
-  const void* kfn = [] {
-    if constexpr (SRC && WALL == 2)
-      return reinterpret_cast<const void*>(&stencil_tbl_conv_src<Real, R, WY, K, Q, NTS, SW>);
-    else if constexpr (SRC && WALL == 1)
-      return reinterpret_cast<const void*>(&stencil_tbl_wall_src<Real, R, WY, K, Q, NTS, SW>);
-    else if constexpr (SRC) return reinterpret_cast<const void*>(&stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>);
-    else if constexpr (WALL == 2) return reinterpret_cast<const void*>(&stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>);
-    else if constexpr (WALL == 1) return reinterpret_cast<const void*>(&stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>);
-    else return reinterpret_cast<const void*>(&stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>);
-  }();
+  constexpr auto kernel = tbl_kernel<Real, R, WY, K, Q, NTS, SW, SRC, EW, WALL>();
+  const void* kfn = reinterpret_cast<const void*>(kernel);
   static_assert(EW == 0 || !SRC, "the edge role has no source form");
   static_assert(!WALL || EW == 0, "the wall form has no edge role");
-  HEAT3D_CHECK(SRC == (p.src != nullptr), "tl: source form mismatch");
-  HEAT3D_CHECK((WALL != 0) == p.has_walls() && (WALL == 2) == p.has_convective(), "tl: wall form mismatch");
+  const SweepForm form = p.form();
+  HEAT3D_CHECK(SRC == form.src, "tl: source form mismatch");
+  HEAT3D_CHECK(WALL == (int)form.wall, "tl: wall form mismatch");
   Box b = p.box;
   constexpr int TY = WY * R + 2 * (EW > 0 ? EW - 1 : 0);  // as the kernel's
   // swap_xy: march along y with x as the tile rows (thin x slabs: a tile of
@@ -375,30 +391,22 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       std::fprintf(stderr, "[heat3d trace] tl K=%d box x %lld: zs=%d L=%d seg=%d tiles=%dx%d blocks=%lld (model %.1f)\n",
                    K, (long long)nxb, zs, Lx, xp.seg, ga.nzb, ga.nyb, (long long)nblocks,
                    xplan_makespan(xp, nxb, tiles, slots, 2 * (K - 1), U));
-    if constexpr (SRC && WALL == 2)
-      hipLaunchKernelGGL((stencil_tbl_conv_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
-                         s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out),
-                         static_cast<const Real*>(p.src), ga, wl, cv, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
-    else if constexpr (SRC && WALL == 1)
-      hipLaunchKernelGGL((stencil_tbl_wall_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
-                         s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out),
-                         static_cast<const Real*>(p.src), ga, wl, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
-    else if constexpr (SRC)
-      hipLaunchKernelGGL((stencil_tbl_src<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
-                         static_cast<const Real*>(p.in), static_cast<Real*>(p.out), static_cast<const Real*>(p.src),
-                         ga, (Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done);
-    else if constexpr (WALL == 2)
-      hipLaunchKernelGGL((stencil_tbl_conv<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
-                         static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, wl, cv, (Real)p.D[0],
-                         (Real)p.D[1], (Real)p.D[2], r, done);
-    else if constexpr (WALL == 1)
-      hipLaunchKernelGGL((stencil_tbl_wall<Real, R, WY, K, Q, NTS, SW>), dim3((unsigned)nblocks), dim3(64 * WY), 0, s,
-                         static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, wl, (Real)p.D[0],
-                         (Real)p.D[1], (Real)p.D[2], r, done);
-    else
-    hipLaunchKernelGGL((stencil_tbl<Real, R, WY, K, Q, NTS, SW, EW>), dim3((unsigned)nblocks), dim3(64 * WY), 0,
-                       s, static_cast<const Real*>(p.in), static_cast<Real*>(p.out), ga, (Real)p.D[0], (Real)p.D[1],
-                       (Real)p.D[2], r, done);
+    // the kernels' arguments, in their order: in, out, [src,] ga, [wl, [cv,]] Dx, Dy, Dz, r, done
+    const auto fields = [&] {
+      const Real* in = static_cast<const Real*>(p.in);
+      Real* out = static_cast<Real*>(p.out);
+      if constexpr (SRC) return std::make_tuple(in, out, static_cast<const Real*>(p.src));
+      else return std::make_tuple(in, out);
+    }();
+    const auto walls = [&] {
+      if constexpr (WALL == 2) return std::make_tuple(wl, cv);
+      else if constexpr (WALL == 1) return std::make_tuple(wl);
+      else return std::make_tuple();
+    }();
+    std::apply(
+        [&](const auto&... a) { hipLaunchKernelGGL(kernel, dim3((unsigned)nblocks), dim3(64 * WY), 0, s, a...); },
+        std::tuple_cat(fields, std::make_tuple(ga), walls,
+                       std::make_tuple((Real)p.D[0], (Real)p.D[1], (Real)p.D[2], r, done)));
     HIPK_CHECK(hipGetLastError());
   };
   if (ks.L == 0 && ks.ZS == 0 && !SW) {
@@ -409,14 +417,8 @@ void launch_tbl(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
       const int wide = 64 - 2 * K, aligned = sizeof(Real) == 8 ? wide & ~7 : wide;
       for (int z : {wide, aligned})
         if (std::find(zs_opts.begin(), zs_opts.end(), z) == zs_opts.end()) zs_opts.push_back(z);
-      tune_schedule(SRC && WALL == 2 ? (sizeof(Real) == 8 ? "tl-fp64-conv-src" : "tl-fp32-conv-src")
-                    : SRC && WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall-src" : "tl-fp32-wall-src")
-                    : SRC    ? (sizeof(Real) == 8 ? "tl-fp64-src" : "tl-fp32-src")
-                    : WALL == 2 ? (sizeof(Real) == 8 ? "tl-fp64-conv" : "tl-fp32-conv")
-                    : WALL ? (sizeof(Real) == 8 ? "tl-fp64-wall" : "tl-fp32-wall")
-                    : sizeof(Real) == 8 ? "tl-fp64" : "tl-fp32",
-                    kfn, box, slots, p.cu_reserved, U, zs_opts, s, fire,
-                    g.nyb, 2 * (K - 1));
+      tune_schedule(tbl_tuning_name<Real, SRC, WALL>(), kfn, box, slots, p.cu_reserved, U, zs_opts, s, fire, g.nyb,
+                    2 * (K - 1));
       return;  // every candidate computed this sweep
     }
     SchedChoice c;

@@ -1,66 +1,30 @@
 // heat3d-mi355x — the insulated-wall forms of the lean K-step sweep ("tl" with
 // StencilParams::wall): instantiation of the variants listed in
-// stencil_tbl_wall_variants.inc and their dispatch.  The kernel is the third
-// textual inclusion of stencil_tbl_kernel.inc (stencil_tbl_impl.hpp,
-// H3D_TBL_WALL): a unit of its own, so the kernels without walls keep their
-// code objects.
-#include "stencil_tbl_impl.hpp"
+// stencil_tbl_wall_variants.inc, and the same list handed to the shared dispatch
+// of the wall forms (stencil_tbl_form.hpp).  The kernel is the third textual
+// inclusion of stencil_tbl_kernel.inc (stencil_tbl_impl.hpp, H3D_TBL_WALL): a
+// unit of its own, so the kernels without walls keep their code objects.
+#include "stencil_tbl_form.hpp"
 
 namespace heat3d {
 namespace hip {
 
 #define H3D_VW(T, R, WY, K, Q, N, S) \
-  template void launch_tbl<T, R, WY, K, Q, N, S, false, 0, true>(const StencilParams&, const KernelSpec&, hipStream_t);
+  template void launch_tbl<T, R, WY, K, Q, N, S, false, 0, 1>(const StencilParams&, const KernelSpec&, hipStream_t);
 #include "stencil_tbl_wall_variants.inc"
 #undef H3D_VW
 
-// With walls the default form is the one-value-per-lane lean kernel for fp32
-// too (the pair kernel has no wall form): an unset V resolves to 1.
-// p == nullptr: only report whether the wall form of k exists.
-template <typename Real>
-static bool dispatch_tbl_wall(const StencilParams* p, const KernelSpec& k, hipStream_t s) {
-  constexpr bool f64 = sizeof(Real) == 8;
-  KernelSpec k1 = k;
-  if (k1.V == 0) k1.V = 1;
-  const KernelSpec r = k1.resolved(f64 ? DType::F64 : DType::F32);
-  const int K = k.K, R = r.R, WY = r.WY, Q = r.NT;
-  if (p) {
-    // the thin x slabs' y-marching tiles, chosen as dispatch_tbl chooses them
-    const Box& bx = p->box;
-    const bool dflt = k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0;
-    if (K == 3 && dflt && bx.extent(0) == 4 && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 2, 5, 3, 3, f64 ? 2 : 0, true, false, 0, true>(*p, k, s);
-      return true;
-    }
-    if (K == 3 && dflt && bx.extent(0) > 0 && bx.extent(0) <= 2 * K && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 3, 3, 3, 3, f64 ? 2 : 0, true, false, 0, true>(*p, k, s);
-      return true;
-    }
-    if (K == 4 && dflt && bx.extent(0) > 0 && bx.extent(0) <= K && bx.extent(1) >= 16 * bx.extent(0)) {
-      launch_tbl<Real, 3, 4, 4, 3, f64 ? 2 : 0, true, false, 0, true>(*p, k, s);
-      return true;
-    }
-  }
-  if (r.V != 1 || r.WZ != 1 || Q != 3 || r.EW != 0) return false;  // (no pair form, no edge role)
-  const int O = r.O > 0 ? r.O : 0;
-#define H3D_TBLW(RR, YY, KK, AA)                                               \
-  if (R == RR && WY == YY && K == KK && O == (AA)) {                           \
-    if (p) launch_tbl<Real, RR, YY, KK, 3, (AA), false, false, 0, true>(*p, k, s); \
-    return true;                                                               \
-  }
-  if constexpr (f64) {
-    H3D_TBLW(3, 16, 3, 2) H3D_TBLW(3, 16, 3, 2 | kResidualLastOnly)
-    H3D_TBLW(3, 12, 4, 2) H3D_TBLW(3, 12, 4, 2 | kResidualLastOnly)
-    H3D_TBLW(5, 16, 2, 2) H3D_TBLW(5, 16, 2, 2 | kResidualLastOnly)
-  } else {
-    H3D_TBLW(3, 16, 3, 0) H3D_TBLW(4, 16, 4, 0) H3D_TBLW(3, 16, 2, 0)
-  }
-#undef H3D_TBLW
-  return false;
-}
+#define H3D_VW(T, R, WY, K, Q, N, S) TblShape<T, R, WY, K, Q, N, S>,
+using Listed = TblShapes<
+#include "stencil_tbl_wall_variants.inc"
+    TblShapesEnd>;
+#undef H3D_VW
+// every default spec runs its own shape
+static constexpr std::array<TblRedirect, 0> kRedirects{};
 
-bool lean_wall_dispatch(DType t, const StencilParams* p, const KernelSpec& k, void* stream) {
-  return t == DType::F64 ? dispatch_tbl_wall<double>(p, k, S(stream)) : dispatch_tbl_wall<float>(p, k, S(stream));
+template <>
+bool lean_form_dispatch<false, 1>(DType t, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape) {
+  return dispatch_tbl_form<false, 1>(t, Listed{}, kRedirects, p, k, s, shape);
 }
 
 }  // namespace hip

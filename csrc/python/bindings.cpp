@@ -239,21 +239,42 @@ PYBIND11_MODULE(_heat3d, m) {
   m.def("insulated_str", &insulated_str);
   m.def("parse_convective", &parse_convective);
   m.def("convective_str", &convective_str);
+  using heat3d::SweepForm;
+  using heat3d::WallKind;
   m.def("lean_conv_supported", [](const std::string& dtype, const std::string& spec) {
-    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true, true);
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), SweepForm{false, WallKind::Convective});
   }, py::arg("dtype"), py::arg("spec"));
   m.def("lean_wall_supported", [](const std::string& dtype, const std::string& spec) {
-    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), false, true);
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), SweepForm{false, WallKind::Insulated});
   }, py::arg("dtype"), py::arg("spec"));
   // ... its wall form with a heat source (convective: the convective form with one)
   m.def("lean_wall_source_supported", [](const std::string& dtype, const std::string& spec, bool convective) {
-    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), true, true, convective);
+    return heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec),
+                                       SweepForm{true, convective ? WallKind::Convective : WallKind::Insulated});
   }, py::arg("dtype"), py::arg("spec"), py::arg("convective") = false);
   m.def("lean_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
     const heat3d::KernelSpec k = heat3d::KernelSpec::parse(spec);
     if (!k.multi_step()) throw UsageError("lean_supported needs a tl2..tl6 kernel");
-    return heat3d::hip::lean_supported(dt_of(dtype), k, with_source);
+    return heat3d::hip::lean_supported(dt_of(dtype), k, SweepForm{with_source, WallKind::None});
   }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false);
+  // the tile (R, WY, SW) the lean sweep's dispatch would launch for a spec in a form (wall: 0 none,
+  // 1 insulated, 2 convective), or None: no such variant, or the packed-pair kernel.  No device access
+  m.def("lean_shape", [](const std::string& dtype, const std::string& spec, bool with_source, int wall) -> py::object {
+    if (wall < 0 || wall > 2) throw UsageError("lean_shape: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    heat3d::hip::LeanShape sh;
+    const SweepForm form{with_source, static_cast<WallKind>(wall)};
+    if (!heat3d::hip::lean_supported(dt_of(dtype), KernelSpec::parse(spec), form)) return py::none();
+    heat3d::hip::lean_dispatch(dt_of(dtype), form, nullptr, KernelSpec::parse(spec), nullptr, &sh);
+    if (sh.WY == 0) return py::none();
+    return py::make_tuple(sh.R, sh.WY, sh.SW);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false, py::arg("wall") = 0);
+  // the lean dispatch's thin-slab rule: the y-marching tile (R, WY) for a box of extent_x planes and
+  // extent_y rows at depth K, or None (tests/_lean_variants.py thin_slab_form is the tests' copy)
+  m.def("lean_thin_slab", [](int K, bool default_spec, int64_t extent_x, int64_t extent_y) -> py::object {
+    heat3d::hip::LeanShape sh;
+    if (!heat3d::hip::lean_thin_slab(K, default_spec, extent_x, extent_y, &sh)) return py::none();
+    return py::make_tuple(sh.R, sh.WY);
+  }, py::arg("K"), py::arg("default_spec"), py::arg("extent_x"), py::arg("extent_y"));
   // is the tv sweep (conductivity form) of the spec's depth built for dtype?  No device access
   m.def("cond_sweep_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
     return heat3d::hip::cond_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec), with_source);
@@ -630,18 +651,22 @@ PYBIND11_MODULE(_heat3d, m) {
                         double ambient, std::array<double, 3> D) {
     const bool fma = build == "fma";
     if (!fma && build != "generic") throw UsageError("conv_row: build is fma or generic");
-    if (dt_of(dt) == DType::F64) {
-      double b[6];
-      for (int f = 0; f < 6; ++f) b[f] = beta[f];
-      auto fn = fma ? cpu::rows_fma::ftcs_row_conv_f64 : cpu::rows_generic::ftcs_row_conv_f64;
-      return fn(reinterpret_cast<const double*>(in_ptr), reinterpret_cast<double*>(out_ptr), n, off[0], off[1], off[2],
-                off[3], kz[0], kz[1], b, ambient, D[0], D[1], D[2]);
-    }
-    float b[6];
-    for (int f = 0; f < 6; ++f) b[f] = (float)beta[f];
-    auto fn = fma ? cpu::rows_fma::ftcs_row_conv_f32 : cpu::rows_generic::ftcs_row_conv_f32;
-    return fn(reinterpret_cast<const float*>(in_ptr), reinterpret_cast<float*>(out_ptr), n, off[0], off[1], off[2],
-              off[3], kz[0], kz[1], b, (float)ambient, (float)D[0], (float)D[1], (float)D[2]);
+    const cpu::RowKernels& rows = fma ? cpu::rows_fma::table : cpu::rows_generic::table;
+    auto run = [&](auto real) {
+      using Real = decltype(real);
+      Real b[6];
+      for (int f = 0; f < 6; ++f) b[f] = (Real)beta[f];
+      cpu::RowArgs<Real> a{};
+      a.in = reinterpret_cast<const Real*>(in_ptr);
+      a.out = reinterpret_cast<Real*>(out_ptr);
+      a.n = n;
+      a.Dx = (Real)D[0], a.Dy = (Real)D[1], a.Dz = (Real)D[2];
+      a.oxm = off[0], a.oxp = off[1], a.oym = off[2], a.oyp = off[3], a.kzm = kz[0], a.kzp = kz[1];
+      a.beta = b;
+      a.tinf = (Real)ambient;
+      return rows.of<Real>().row[0][(int)heat3d::WallKind::Convective](a);
+    };
+    return dt_of(dt) == DType::F64 ? run(double()) : run(float());
   }, py::arg("build"), py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("off"),
      py::arg("kz"), py::arg("beta"), py::arg("ambient"), py::arg("D"));
   ck.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,

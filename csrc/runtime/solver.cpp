@@ -551,7 +551,10 @@ void Solver::preflight_extra_field(const char* what, std::size_t extra) {
 }
 
 bool Solver::lean_ok(const KernelSpec& ks) const {
-  return hip::lean_supported(dt_, ks, has_source_, walls_ != 0, conv_ != 0);
+  const SweepForm form{has_source_, conv_ != 0    ? WallKind::Convective
+                                    : walls_ != 0 ? WallKind::Insulated
+                                                  : WallKind::None};
+  return hip::lean_supported(dt_, ks, form);
 }
 
 void Solver::set_walls(StencilParams& sp, const Local& l) const {
