@@ -215,6 +215,16 @@ struct LeanShape {
 // V, R, WY, Q field) runs as y-marching tiles of WY waves x R x-rows: 5 x 2 for
 // the 4-plane slabs of a K = 3 sweep, 3 x 3 for its other slabs of up to 2K
 // planes, 4 x 3 for slabs of up to K = 4 planes.  false: the x-marching tile.
+// Why: 3-wave tiles of 9 x-rows marching along y (launch_tbl swap_xy) instead
+// of 48-row tiles marching 3 planes plus a 4-plane pipeline fill along x.
+// Phantom rank of the 1024^3 fp64 slab bench (64 GB/s emulated links): 8 ranks
+// 0.2135 -> 0.2084 ms per step, 4 ranks 0.379 -> 0.359, 2 ranks unchanged
+// (profiles/boundary_slabs_r02.md).  4-plane slabs of a K = 3 sweep before a
+// long sweep (Solver::enqueue_multi thick): 5-wave tiles of 10 x-rows store all
+// 4 planes in one tile; the (K+1)-plane boundary slabs of long sweeps across x
+// halos (K = 4): 4-wave tiles of 12 x-rows store the 4 slab planes.
+// Each tile is tied to its depth here, and every form's list has the three
+// tiles at those depths (SW lines) in both dtypes.
 inline bool lean_thin_slab(int K, bool default_spec, int64_t extent_x, int64_t extent_y, LeanShape* shape) {
   if (!default_spec || extent_x <= 0 || extent_y < 16 * extent_x) return false;
   if (K == 3 && extent_x == 4) *shape = {2, 5, true};

@@ -1,11 +1,13 @@
-// heat3d-mi355x — the dispatch of the lean sweep's wall forms (insulated or
-// convective walls, each with or without a heat source), written once.  Every
-// form has a unit of its own (stencil_tbl_wall.hip, _conv, _wall_src,
-// _conv_src) that instantiates exactly the variants of its list
-// (stencil_tbl_*_variants.inc) and hands the same list, as types, to
-// dispatch_tbl_form: the shapes a unit can launch are the shapes it lists and
-// no others.  What differs between the forms is data: the list, and the
-// default shapes that run in another shape (TblRedirect).
+// heat3d-mi355x — the dispatch of the lean sweep's six forms (with or without a
+// heat source; no, insulated or convective walls), written once.  Every form
+// has a list (stencil_tbl_*_variants.inc) whose lines are instantiated exactly
+// (the forms without walls by the stencil_tbl_part*.hip units, each wall form
+// by a unit of its own: stencil_tbl_wall.hip, _conv, _wall_src, _conv_src) and
+// handed, as types, to dispatch_tbl_form: the dispatch is the list, so what a
+// form can launch is what it lists and nothing else.  What differs between the
+// forms is data: the list, and the default shapes that run in another shape
+// (TblRedirect).  The one thing beside the lists is the packed-pair kernel
+// (stencil_tbp.hip), which only the form without source and walls has.
 #pragma once
 
 #include <array>
@@ -16,8 +18,9 @@
 namespace heat3d {
 namespace hip {
 
-// one line of a variant list: H3D_Vx(Real, R, WY, K, Q, NTS, SW)
-template <typename T, int R, int WY, int K, int Q, int NTS, bool SW>
+// one line of a variant list: H3D_Vx(Real, R, WY, K, Q, NTS, SW), and the edge
+// role EW of an H3D_VE line (spec field 9; 0 on every other line)
+template <typename T, int R, int WY, int K, int Q, int NTS, bool SW, int EW = 0>
 struct TblShape {};
 template <typename... Shapes>
 struct TblShapes {};
@@ -33,9 +36,8 @@ struct TblRedirect {
   int K, R, WY, O, toR, toWY;
 };
 
-// The dispatch of form (SRC, WALL): stencil_tbl.hip has <*, 0> (dispatch_tbl,
-// dispatch_tbl_src), each wall form's unit its own.  kernels.hpp lean_dispatch
-// is the table of the six.
+// The dispatch of form (SRC, WALL): stencil_tbl.hip has <*, 0>, each wall
+// form's unit its own.  kernels.hpp lean_dispatch is the table of the six.
 template <bool SRC, int WALL>
 bool lean_form_dispatch(DType t, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape);
 template <> bool lean_form_dispatch<false, 0>(DType, const StencilParams*, const KernelSpec&, hipStream_t, LeanShape*);
@@ -49,41 +51,53 @@ template <> bool lean_form_dispatch<true, 2>(DType, const StencilParams*, const 
 struct TblWant {
   int R, WY, K, Q, O;
   bool SW;
+  int EW = 0;
 };
 
-template <typename Real, bool SRC, int WALL, typename T, int R, int WY, int K, int Q, int NTS, bool SW>
-bool launch_if_listed(TblShape<T, R, WY, K, Q, NTS, SW>, const TblWant& w, const StencilParams* p, const KernelSpec& k,
+template <typename Real, bool SRC, int WALL, typename T, int R, int WY, int K, int Q, int NTS, bool SW, int EW>
+bool launch_if_listed(TblShape<T, R, WY, K, Q, NTS, SW, EW>, const TblWant& w, const StencilParams* p, const KernelSpec& k,
                       hipStream_t s) {
   if constexpr (std::is_same_v<T, Real>) {  // (launch_tbl is named for the list's own lines only)
-    if (w.R == R && w.WY == WY && w.K == K && w.Q == Q && w.O == NTS && w.SW == SW) {
-      if (p) launch_tbl<Real, R, WY, K, Q, NTS, SW, SRC, 0, WALL>(*p, k, s);
+    if (w.R == R && w.WY == WY && w.K == K && w.Q == Q && w.O == NTS && w.SW == SW && w.EW == EW) {
+      if (p) launch_tbl<Real, R, WY, K, Q, NTS, SW, SRC, EW, WALL>(*p, k, s);
       return true;
     }
   }
   return false;
 }
 
-// With walls the default form is the one-value-per-lane lean kernel for fp32
-// too (the pair kernel has no wall form): an unset V resolves to 1.
+// With a source or walls the default form is the one-value-per-lane lean
+// kernel for fp32 too (the pair kernel has no such form): an unset V resolves
+// to 1.  Without either, a spec resolving to V = 2 (two columns per lane: packed
+// fp32 / 16-byte fp64 pairs) goes to the pair kernel, which reports no shape.
+// The edge role is a field of a list line; no source or wall list has one.
 // p == nullptr: only report whether the form of k exists (and its shape).
 template <typename Real, bool SRC, int WALL, typename... Shapes, std::size_t N>
 bool dispatch_tbl_form_t(TblShapes<Shapes...>, const std::array<TblRedirect, N>& redirects, const StencilParams* p,
                          const KernelSpec& k, hipStream_t s, LeanShape* shape) {
   constexpr bool f64 = sizeof(Real) == 8;
+  constexpr DType t = f64 ? DType::F64 : DType::F32;
+  constexpr bool pairs = !SRC && WALL == 0;
   KernelSpec k1 = k;
-  if (k1.V == 0) k1.V = 1;
-  const KernelSpec r = k1.resolved(f64 ? DType::F64 : DType::F32);
-  TblWant w{r.R, r.WY, k.K, r.NT, r.O > 0 ? r.O : 0, false};
+  if (!pairs && k1.V == 0) k1.V = 1;
+  const KernelSpec r = k1.resolved(t);
+  TblWant w{r.R, r.WY, k.K, r.NT, r.O > 0 ? r.O : 0, false, r.EW};
   for (const TblRedirect& d : redirects)
     if (d.f64 == f64 && d.K == w.K && d.R == w.R && d.WY == w.WY && d.O == w.O) {
       w.R = d.toR, w.WY = d.toWY;
       break;
     }
   LeanShape thin;
-  if (p && lean_thin_slab(k.K, k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0, p->box.extent(0), p->box.extent(1), &thin))
+  if (p && lean_thin_slab(k.K, k.V == 0 && k.R == 0 && k.WY == 0 && k.NT == 0, p->box.extent(0), p->box.extent(1), &thin)) {
     w = TblWant{thin.R, thin.WY, k.K, 3, f64 ? 2 : 0, true};
-  else if (r.V != 1 || r.WZ != 1 || r.EW != 0)
-    return false;  // (no pair form, no edge role)
+  } else if (pairs && r.V == 2) {
+    if (r.EW != 0) return false;  // (no edge role there)
+    if (!p) return lean_pair_supported(t, k);
+    stencil_lean_pair(t, *p, k, s);
+    return true;
+  } else if (r.V != 1 || r.WZ != 1) {
+    return false;  // one value per lane, one wave across z
+  }
   const bool ok = (launch_if_listed<Real, SRC, WALL>(Shapes{}, w, p, k, s) || ...);
   if (ok && shape) *shape = LeanShape{w.R, w.WY, w.SW};
   return ok;

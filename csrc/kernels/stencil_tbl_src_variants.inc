@@ -4,8 +4,9 @@
 // default at the default depth 3: the K = 3 sweep, the long K = 4 sweep and the
 // partial K = 2 sweep, fp64 with every residual and with the last one only (fp32
 // source runs compute every residual), and the y-marching thin-slab forms.
-// dispatch_tbl_src (stencil_tbl.hip) names every entry; any other spec with a
-// source is an error.
+// The dispatch is this list (stencil_tbl.hip hands it, as types, to
+// stencil_tbl_form.hpp dispatch_tbl_form); any other spec with a source is an
+// error.  There is no edge role with a source.
 H3D_VS(double, 2, 5, 3, 3, 2, true, 0)
 H3D_VS(double, 3, 3, 3, 3, 2, true, 1)
 H3D_VS(double, 3, 4, 4, 3, 2, true, 3)

@@ -2,7 +2,8 @@
 stencil_tbl_src_variants.inc) as the test matrix: every H3D_V / H3D_VE / H3D_VS
 line becomes a record, and every record that a kernel spec can select becomes a
 spec string.  tests/test_lean_variants_cpu.py ties the table to the dispatch
-(stencil_tbl.hip), tests/test_gpu_lean_variants.py launches every entry."""
+(stencil_tbl_form.hpp dispatch_tbl_form, which stencil_tbl.hip hands the same
+lists), tests/test_gpu_lean_variants.py launches every entry."""
 import os
 import re
 from collections import namedtuple
@@ -75,8 +76,8 @@ def plain():
 
 
 def thin_slab_form(K, box_extent_x, box_extent_y, default_spec=True):
-    """dispatch_tbl's choice of a y-marching (SW) form by box shape, as
-    (R, WY, K), or None: the x-marching tile."""
+    """The lean dispatch's choice of a y-marching (SW) form by box shape
+    (kernels.hpp lean_thin_slab), as (R, WY, K), or None: the x-marching tile."""
     ex, ey = box_extent_x, box_extent_y
     if not default_spec or ex <= 0 or ey < 16 * ex:
         return None

@@ -1,7 +1,7 @@
-"""The lean sweep's form dispatch (no GPU): the thin-slab rule of the five
-dispatch functions against the tests' copy of it, and the tile every default
-spec runs as in each of the six forms (source or none x no, insulated or
-convective walls) against that form's variant list."""
+"""The lean sweep's form dispatch (no GPU): its thin-slab rule against the
+tests' copy of it, and the tile every default spec and every listed line runs
+as in each of the six forms (source or none x no, insulated or convective
+walls) against that form's variant list."""
 import itertools
 import os
 import re
@@ -41,6 +41,14 @@ def _listed(form):
         out.add(("fp64" if m.group(1) == "double" else "fp32", *map(int, f[:5]), f[5] == "true"))
     assert len(out) == len(re.findall(r"^" + macro + r"\(", text, re.M)) and out
     return out
+
+
+def _edge_listed():
+    """(dtype, R, WY, K, Q, NTS, SW, EW) of the edge-role lines (the plain form's list alone has any)."""
+    for form, (name, macro) in LISTS.items():
+        with open(os.path.join(lv.KERNELS, name)) as f:
+            assert (macro + "E(" in f.read()) == (form == (False, 0)), name
+    return {(v.dtype, v.R, v.WY, v.K, v.Q, v.NTS, v.SW, v.EW) for v in lv.variants() if v.EW}
 
 
 def _supported(ext, dtype, spec, src, wall):
@@ -97,3 +105,25 @@ def test_redirections_name_listed_shapes_only():
         assert (dtype, *to, K) in shapes, (src, wall, dtype, K, last, to)
         own = {("fp64", 2): (5, 16), ("fp64", 3): (3, 16), ("fp64", 4): (3, 12), ("fp32", 4): (4, 16)}[(dtype, K)]
         assert (dtype, *own, K) not in shapes, (src, wall, dtype, K, last, own)
+
+
+@pytest.mark.parametrize("src,wall", sorted(LISTS))
+def test_a_listed_line_runs_as_itself(ext, src, wall):
+    """The spec that names a spec-selectable (non-SW) line of a form's list runs
+    that line's tile: a listed line is never redirected (the premise is
+    test_redirections_name_listed_shapes_only).  Edge-role lines carry field 9."""
+    lines = {(*line, 0) for line in _listed((src, wall))}
+    if (src, wall) == (False, 0):
+        edge = _edge_listed()
+        assert edge and not edge & lines
+        lines |= edge
+    seen = 0
+    for dtype, R, WY, K, Q, NTS, SW, EW in sorted(lines):
+        if SW:
+            continue
+        spec = lv.spec(lv.Variant(dtype, R, WY, K, Q, NTS, SW, EW, src))
+        assert len(spec.split(":")) == (10 if EW else 8) and (not EW or spec.endswith(f":{EW}")), spec
+        assert _supported(ext, dtype, spec, src, wall), (dtype, spec)
+        assert ext.lean_shape(dtype, spec, src, wall) == (R, WY, False), (dtype, spec)
+        seen += 1
+    assert seen == len(lines) - 6  # three thin-slab (SW) lines per dtype in every list

@@ -89,7 +89,7 @@ def test_a_dropped_entry_is_noticed(ext, tmp_path):
 
 def test_thin_slab_forms_listed():
     """The y-marching forms are picked by box shape: the three tile shapes of
-    dispatch_tbl / dispatch_tbl_src, in both dtypes, with and without a source."""
+    lean_thin_slab, in both dtypes, with and without a source."""
     sw = [v for v in lv.variants() if v.SW]
     shapes = {(2, 5, 3), (3, 3, 3), (3, 4, 4)}
     assert {(v.dtype, v.src, (v.R, v.WY, v.K)) for v in sw} == set(itertools.product(DTYPES, (False, True), shapes))
