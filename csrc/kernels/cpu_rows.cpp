@@ -69,16 +69,43 @@ static double row(const RowArgs<Real>& a) {
   return row_loop<Real, SRC, WALL>(a.in, a.out, a.src, a);
 }
 
-template <typename Real, bool SRC>
-static inline double row_var(const Real* __restrict in, Real* __restrict out, const Real* __restrict h,
-                             const Real* __restrict src, int64_t n, int64_t sx, int64_t sy, Real Dx, Real Dy,
-                             Real Dz) {
+// The update with a conductivity in the form (SRC, WALL).  Behind a wall only
+// the neighbour's temperature is replaced, exactly as in the uniform row above
+// (the centre value behind an insulated face, convective_ghost behind a
+// convective one); the face weights stay Ch[c] + Ch[neighbour], Ch read at the
+// wall vertex.  Then ftcs_update_var, then the source: the order and the
+// arithmetic of a single step on refreshed wall planes, so the flux through an
+// insulated face is w * (c - c) = +0.
+template <typename Real, bool SRC, WallKind WALL>
+static inline double row_var_loop(const Real* __restrict in, Real* __restrict out, const Real* __restrict h,
+                                  [[maybe_unused]] const Real* __restrict src, const RowArgs<Real>& a) {
+  const int64_t n = a.n;
+  const Real Dx = a.Dx, Dy = a.Dy, Dz = a.Dz;
+  const int64_t sx = a.sx, sy = a.sy;
+  [[maybe_unused]] const int64_t oxm = a.oxm, oxp = a.oxp, oym = a.oym, oyp = a.oyp, kzm = a.kzm, kzp = a.kzp;
+  [[maybe_unused]] Real bxm = 0, bxp = 0, bym = 0, byp = 0, bzm = 0, bzp = 0, tinf = 0;
+  if constexpr (WALL == WallKind::Convective) {
+    bxm = a.beta[0], bxp = a.beta[1], bym = a.beta[2], byp = a.beta[3], bzm = a.beta[4], bzp = a.beta[5];
+    tinf = a.tinf;
+  }
   double lres = 0.0;
   bool nan = false;
   for (int64_t k = 0; k < n; ++k) {
     const Real T = in[k];
-    Real nv = ftcs_update_var<Real>(T, in[k - sx], in[k + sx], in[k - sy], in[k + sy], in[k - 1], in[k + 1], h[k],
-                                    h[k - sx], h[k + sx], h[k - sy], h[k + sy], h[k - 1], h[k + 1], Dx, Dy, Dz);
+    Real xm, xp, ym, yp, zm, zp;
+    if constexpr (WALL == WallKind::None) {
+      xm = in[k - sx], xp = in[k + sx], ym = in[k - sy], yp = in[k + sy], zm = in[k - 1], zp = in[k + 1];
+    } else if constexpr (WALL == WallKind::Insulated) {
+      xm = in[k + oxm], xp = in[k + oxp], ym = in[k + oym], yp = in[k + oyp];
+      zm = k == kzm ? T : in[k - 1], zp = k == kzp ? T : in[k + 1];
+    } else {
+      const Real d = tinf - T;
+      xm = oxm ? in[k + oxm] : h3d_fma(bxm, d, T), xp = oxp ? in[k + oxp] : h3d_fma(bxp, d, T);
+      ym = oym ? in[k + oym] : h3d_fma(bym, d, T), yp = oyp ? in[k + oyp] : h3d_fma(byp, d, T);
+      zm = k == kzm ? h3d_fma(bzm, d, T) : in[k - 1], zp = k == kzp ? h3d_fma(bzp, d, T) : in[k + 1];
+    }
+    Real nv = ftcs_update_var<Real>(T, xm, xp, ym, yp, zm, zp, h[k], h[k - sx], h[k + sx], h[k - sy], h[k + sy],
+                                    h[k - 1], h[k + 1], Dx, Dy, Dz);
     if constexpr (SRC) nv = add_source<Real>(nv, src[k]);
     out[k] = nv;
     const double d = resid_abs(nv, T);
@@ -88,10 +115,9 @@ static inline double row_var(const Real* __restrict in, Real* __restrict out, co
   return nan ? std::nan("") : lres;
 }
 
-template <typename Real>
-static double row_var_any(const RowArgs<Real>& a) {
-  return a.src ? row_var<Real, true>(a.in, a.out, a.cond, a.src, a.n, a.sx, a.sy, a.Dx, a.Dy, a.Dz)
-               : row_var<Real, false>(a.in, a.out, a.cond, nullptr, a.n, a.sx, a.sy, a.Dx, a.Dy, a.Dz);
+template <typename Real, bool SRC, WallKind WALL>
+static double row_var(const RowArgs<Real>& a) {
+  return row_var_loop<Real, SRC, WALL>(a.in, a.out, a.cond, a.src, a);
 }
 
 template <typename Real>
@@ -99,7 +125,8 @@ static constexpr RowTable<Real> make_table() {
   constexpr WallKind N = WallKind::None, I = WallKind::Insulated, C = WallKind::Convective;
   return {{{row<Real, false, N>, row<Real, false, I>, row<Real, false, C>},
            {row<Real, true, N>, row<Real, true, I>, row<Real, true, C>}},
-          row_var_any<Real>};
+          {{row_var<Real, false, N>, row_var<Real, false, I>, row_var<Real, false, C>},
+           {row_var<Real, true, N>, row_var<Real, true, I>, row_var<Real, true, C>}}};
 }
 
 // (constant-initialised: nothing of this build runs before it is chosen)

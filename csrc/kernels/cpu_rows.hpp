@@ -10,8 +10,8 @@
 //
 // One row template covers the forms of the uniform update (kernels.hpp
 // SweepForm: with or without a heat source, behind no, insulated or convective
-// walls), a second one the update with a conductivity field.  Every row has
-// the same signature, and each build exports one table of them.
+// walls), a second one the same forms of the update with a conductivity field.
+// Every row has the same signature, and each build exports one table of them.
 #pragma once
 
 #include <cstdint>
@@ -33,7 +33,8 @@ struct RowArgs {
   const Real* cond;  // conductivity form (ftcs_update_var; with src != nullptr ftcs_update_var_src)
   int64_t sx, sy;    // strides of the x and y neighbours (the forms without walls)
   // walls (StencilParams::wall): the offsets of the x and y neighbours, 0 where
-  // the neighbour across a wall is replaced by the ghost value, and the row
+  // the neighbour's temperature across a wall is replaced by the ghost value
+  // (the conductivity forms still read Ch at the wall vertex: sx, sy), and the row
   // indices whose z- / z+ neighbour is (-1 or beyond n: none).  The ghost is
   // the centre value behind insulated walls, convective_ghost(T, beta, tinf)
   // behind convective ones (the ghost substitution comes first, then the source)
@@ -51,7 +52,9 @@ using RowFn = double (*)(const RowArgs<Real>&);
 template <typename Real>
 struct RowTable {
   RowFn<Real> row[2][3];  // [SweepForm::src][SweepForm::wall]
-  RowFn<Real> var;        // the conductivity form
+  RowFn<Real> var[2][3];  // the conductivity forms, by the same indices
+  // the row of a call: its form, and whether it has a conductivity
+  RowFn<Real> of(SweepForm f, bool cond) const { return (cond ? var : row)[f.src][(int)f.wall]; }
 };
 
 struct RowKernels {

@@ -98,7 +98,8 @@ struct StencilParams {
   // towards a ghost point reads Ch there).  Every updated point is evaluated
   // by ftcs_update_var.  nullptr: uniform material, the kernels above.  The
   // single-step kernels and the tv sweeps have a conductivity form (a tl sweep
-  // with it is an error, as is a tv sweep without it).
+  // with it is an error, as is a tv sweep without it).  Together with `wall`
+  // below: cpu::stencil / stencil_multi and the wall forms of the tv sweep.
   const void* cond = nullptr;
   // Insulated (zero-flux) walls: wall[a][0] / wall[a][1] is the local
   // coordinate along axis a of the updated plane (row, column) next to the
@@ -108,11 +109,13 @@ struct StencilParams {
   // ghost; the flux through the face between them is exactly 0) and the update
   // is evaluated as ever.  Taken from global indices, so it also holds for
   // wall-adjacent points computed inside a neighbour's deep halo.  cpu::stencil
-  // and cpu::stencil_multi honour it, also with a source (not with a
-  // conductivity: that runs as single steps on wall planes copied from their
-  // inward neighbours), as do the wall forms of the lean sweep
-  // (stencil_tbl_wall.hip; with a source stencil_tbl_wall_src.hip); the
-  // single-step gfx950 kernels do not take it.
+  // and cpu::stencil_multi honour it, also with a source and with a
+  // conductivity (only the neighbour's temperature is replaced: the face
+  // weights still read Ch at the wall vertex), as do the wall forms of the lean
+  // sweep (stencil_tbl_wall.hip; with a source stencil_tbl_wall_src.hip) and of
+  // the tv sweep (stencil_tbv_wall.hip); the single-step gfx950 kernels do not
+  // take it (they run on wall planes copied from their inward neighbours,
+  // which gives the same bits).
   int64_t wall[3][2] = {{kNoWall, kNoWall}, {kNoWall, kNoWall}, {kNoWall, kNoWall}};
   // Convective (Robin) walls, -k dT/dn = h (T - T_inf): a face with a wall
   // coordinate above and wall_beta[a][e] >= 0 is convective with that
@@ -123,7 +126,7 @@ struct StencilParams {
   // insulated faces of the same call are evaluated as coefficient 0 (every
   // backend alike).  Honoured where `wall` is: cpu::stencil / stencil_multi and
   // the convective forms of the lean sweep (stencil_tbl_conv.hip; with a source
-  // stencil_tbl_conv_src.hip).
+  // stencil_tbl_conv_src.hip) and of the tv sweep (stencil_tbv_conv.hip).
   double wall_beta[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
   double ambient = 0;
   // the one place that reads src, wall and wall_beta for the form of the call
@@ -244,12 +247,19 @@ bool lean_dispatch(DType t, SweepForm form, const StencilParams* p, const Kernel
 void refresh_convective(DType t, void* f, const Layout& L, const Box& bs, const Box& bd, double beta,
                         double ambient, void* stream);
 // K-step sweep with a conductivity field (stencil_tbv.hip; spec tvK): needs
-// p.cond, honours p.src; no fused check, no schedule tuning
+// p.cond, honours p.src and p.wall / p.wall_beta (the wall forms of
+// stencil_tbv_wall.hip / stencil_tbv_conv.hip; a form that is not built is an
+// Error naming it, and nothing is written); no fused check, no schedule tuning
 void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
-// Is the tv kernel of k's depth built for dtype t (with_source: its heat-source form)?
+// Is the tv kernel of k's depth built for dtype t in the given form (source
+// flag and wall kind, StencilParams::form)?  *shape, if given, receives the
+// tile (R rows x WY waves) that runs it.  No device access.
+bool cond_sweep_supported(DType t, const KernelSpec& k, SweepForm form = {}, LeanShape* shape = nullptr);
+// (the form without walls; with_source: its heat-source form)
 bool cond_sweep_supported(DType t, const KernelSpec& k, bool with_source);
-// deepest tv depth built for dtype t
-int cond_sweep_max_depth(DType t);
+// deepest tv depth built for dtype t in the given form, every shallower depth
+// down to 2 being built in it too (0: none)
+int cond_sweep_max_depth(DType t, SweepForm form = {});
 // Any multi-step kind -> its kernel
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 void pack_box(DType t, const void* f, const Layout& L, const Box& b, void* buf, void* stream);

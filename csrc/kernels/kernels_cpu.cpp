@@ -72,11 +72,7 @@ static void stencil_t(const StencilParams& p) {
   unsigned long long resbits = 0;
   // the row of the call's form (cpu_rows.hpp): one lookup, one call per row
   const SweepForm form = p.form();
-  HEAT3D_CHECK(form.wall == WallKind::None || !p.cond,
-               "cpu::stencil: insulated / convective walls with a conductivity run as single steps on copied wall "
-               "planes, not through StencilParams::wall");
-  const RowTable<Real>& rows = cpu_row_kernels().of<Real>();
-  const RowFn<Real> rowfn = p.cond ? rows.var : rows.row[form.src][(int)form.wall];
+  const RowFn<Real> rowfn = cpu_row_kernels().of<Real>().of(form, p.cond != nullptr);
   // convective walls (StencilParams::wall_beta): the coefficients in the
   // field's dtype, 0 on the insulated faces of the same call
   Real beta[6];

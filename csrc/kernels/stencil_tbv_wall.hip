@@ -1,0 +1,38 @@
+// heat3d-mi355x — the insulated-wall forms of the tv sweep (K-step sweeps with a
+// conductivity field, stencil_tbv.hip): the kernel stencil_tbv_wall of
+// stencil_tbv_impl.hpp, instantiated here, in a unit of its own, so that the
+// kernels without walls keep their device code.  Every shape computes the same
+// bits; each form runs in the shape of the form without walls where that needs
+// no scratch, else in one of fewer waves or rows that does not (register report
+// and the shapes tried: profiles/cond_wall_sweeps.md).  A form that has no
+// scratch-free shape of at least 8 waves has no line: it is not built, and the
+// solver runs a shallower depth or single steps instead.
+#include "stencil_tbv_impl.hpp"
+
+namespace heat3d {
+namespace hip {
+
+template <typename Real>
+static bool dispatch(bool src, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape) {
+#define H3D_FORM(SRCB, KK, RR, YY) H3D_TBV_WALL_SHAPE(1, SRCB, KK, RR, YY)
+  if constexpr (sizeof(Real) == 8) {
+    H3D_FORM(false, 2, 2, 16)
+    H3D_FORM(true, 2, 2, 16)
+    H3D_FORM(false, 3, 2, 12)
+    H3D_FORM(true, 3, 3, 8)    // 2 x 12 needs 24 B of scratch: the same 24-row tile on 8 waves
+  } else {
+    H3D_FORM(false, 2, 5, 16)
+    H3D_FORM(true, 2, 4, 16)   // 5 x 16 needs 36 B of scratch
+    H3D_FORM(false, 3, 4, 12)
+    H3D_FORM(true, 3, 3, 12)   // 4 x 12 needs 12 B of scratch
+  }
+#undef H3D_FORM
+  return false;
+}
+
+bool tbv_wall_dispatch(DType t, bool src, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape) {
+  return t == DType::F64 ? dispatch<double>(src, p, k, s, shape) : dispatch<float>(src, p, k, s, shape);
+}
+
+}  // namespace hip
+}  // namespace heat3d

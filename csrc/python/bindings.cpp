@@ -276,9 +276,27 @@ PYBIND11_MODULE(_heat3d, m) {
     return py::make_tuple(sh.R, sh.WY);
   }, py::arg("K"), py::arg("default_spec"), py::arg("extent_x"), py::arg("extent_y"));
   // is the tv sweep (conductivity form) of the spec's depth built for dtype?  No device access
-  m.def("cond_sweep_supported", [](const std::string& dtype, const std::string& spec, bool with_source) {
-    return heat3d::hip::cond_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec), with_source);
-  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false);
+  // (wall: 0 none, 1 insulated, 2 convective: its wall form)
+  m.def("cond_sweep_supported", [](const std::string& dtype, const std::string& spec, bool with_source, int wall) {
+    if (wall < 0 || wall > 2) throw UsageError("cond_sweep_supported: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    return heat3d::hip::cond_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec),
+                                             SweepForm{with_source, static_cast<WallKind>(wall)});
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false, py::arg("wall") = 0);
+  // the tile (R, WY) that runs the tv sweep of the spec's depth in a form, or None: that form is not
+  // built.  No device access
+  m.def("cond_sweep_shape", [](const std::string& dtype, const std::string& spec, bool with_source, int wall) -> py::object {
+    if (wall < 0 || wall > 2) throw UsageError("cond_sweep_shape: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    heat3d::hip::LeanShape sh;
+    if (!heat3d::hip::cond_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec),
+                                           SweepForm{with_source, static_cast<WallKind>(wall)}, &sh))
+      return py::none();
+    return py::make_tuple(sh.R, sh.WY);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false, py::arg("wall") = 0);
+  // the deepest tv depth built for dtype in a form (0: none)
+  m.def("cond_sweep_max_depth", [](const std::string& dtype, bool with_source, int wall) {
+    if (wall < 0 || wall > 2) throw UsageError("cond_sweep_max_depth: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    return heat3d::hip::cond_sweep_max_depth(dt_of(dtype), SweepForm{with_source, static_cast<WallKind>(wall)});
+  }, py::arg("dtype"), py::arg("with_source") = false, py::arg("wall") = 0);
   m.def("rccl_unique_id", []() { return py::bytes(rccl_unique_id()); });
   m.def("rccl_version", &rccl_version);
   // the HIP runtime / RCCL this process is bound to (bench JSON "runtime")

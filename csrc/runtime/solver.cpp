@@ -280,7 +280,7 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
   for (int a = 0; a < 3; ++a) fits &= dims[a] == 1 || min_n[a] >= K;
   tb_ = kspec_.kind != KernelSpec::Naive && (cfg_.temporal >= 2 || (cfg_.temporal == 0 && be_->is_gpu())) && fits;
   K_ = tb_ ? K : 1;
-  Kc_ = !tb_ ? 0 : be_->is_gpu() ? std::min(K_, hip::cond_sweep_max_depth(dt_)) : K_;
+  set_cond_depth();
   for (int a = 0; a < 3; ++a) hd_[a] = xd_[a] = tb_ && dims[a] > 1 ? K : 1;
   ordered_halo_ = tb_ && block;
   // overlapped sweeps need a non-empty interior between the boundary layers
@@ -550,11 +550,10 @@ void Solver::preflight_extra_field(const char* what, std::size_t extra) {
   planned_bytes_ += extra;
 }
 
-bool Solver::lean_ok(const KernelSpec& ks) const {
-  const SweepForm form{has_source_, conv_ != 0    ? WallKind::Convective
-                                    : walls_ != 0 ? WallKind::Insulated
-                                                  : WallKind::None};
-  return hip::lean_supported(dt_, ks, form);
+bool Solver::lean_ok(const KernelSpec& ks) const { return hip::lean_supported(dt_, ks, sweep_form()); }
+
+void Solver::set_cond_depth() {
+  Kc_ = !tb_ ? 0 : be_->is_gpu() ? std::min(K_, hip::cond_sweep_max_depth(dt_, sweep_form())) : K_;
 }
 
 void Solver::set_walls(StencilParams& sp, const Local& l) const {
@@ -714,6 +713,7 @@ void Solver::initialize() {
 // from it (initialize(); again when a heat source is set or cleared: the
 // source forms are kernels of their own, timed on their own)
 void Solver::retune() {
+  set_cond_depth();
   sweep_costs_.clear();
   if (sweep_form_auto()) {  // re-timed from the lean form on every initialisation
     KernelSpec lean;

@@ -314,16 +314,19 @@ class Solver {
   // tv sweeps asked for)
   bool sweeping() const { return tb_ && (!has_cond_ || cond_sweeping()) && !walls_single(); }
   // ... of the tv family, with the conductivity field (--conductivity-sweeps)
-  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2 && !walls_; }
+  // (behind walls too: the wall forms of the tv kernels)
+  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2; }
   // Insulated walls (Config::insulated).  Sweeps run the wall forms of the
   // lean kernel (StencilParams::wall: the substitution happens in the kernel,
   // at every stage).  Single steps run the kernels as they are on wall planes
   // refreshed from their inward neighbours (refresh_walls), which gives the
-  // same bits.  With a conductivity as well there is no sweep form: every
-  // iteration is such a single step (walls_single).  With a source there is
-  // one (the wall forms with a source, stencil_tbl_wall_src.hip and
-  // stencil_tbl_conv_src.hip), used where Config::wall_source_sweeps asks for
-  // it; by default a source with walls runs as single steps too.
+  // same bits.  With a conductivity as well the sweeps are the wall forms of
+  // the tv kernels (stencil_tbv_wall.hip, stencil_tbv_conv.hip), used where
+  // Config::cond_sweeps asks for tv sweeps, source or not; without it every
+  // iteration is such a single step (walls_single).  With a source and no
+  // conductivity there are the wall forms with a source (stencil_tbl_wall_src.hip
+  // and stencil_tbl_conv_src.hip), used where Config::wall_source_sweeps asks
+  // for them; by default a source with walls runs as single steps too.
   // Convective walls (Config::convective, ambient) are walls in all of this:
   // walls_ holds the insulated and the convective faces, conv_ the convective
   // ones with their coefficients in conv_beta_.  Their sweeps run the
@@ -332,7 +335,15 @@ class Solver {
   // the wall plane with the ghost values (Backend::refresh_convective).
   unsigned walls_ = 0, conv_ = 0;
   double conv_beta_[6] = {-1, -1, -1, -1, -1, -1};
-  bool walls_single() const { return walls_ && (has_cond_ || (has_source_ && !cfg_.wall_source_sweeps)); }
+  bool walls_single() const {
+    return walls_ && (has_cond_ ? !cond_sweeping() : has_source_ && !cfg_.wall_source_sweeps);
+  }
+  // the form of this run's sweeps: a source or not, behind which kind of wall
+  SweepForm sweep_form() const {
+    return SweepForm{has_source_, conv_ != 0    ? WallKind::Convective
+                                  : walls_ != 0 ? WallKind::Insulated
+                                                : WallKind::None};
+  }
   void set_walls(StencilParams& sp, const Local& l) const;
   // wall planes of buffer b <- their inward neighbours, axis order x, y, z,
   // over the whole local extent of the other axes (ghosts included); vertices
@@ -343,7 +354,10 @@ class Solver {
   // steps per sweep of the schedule: K_, or the tv sweeps' depth Kc_ <= K_ (a
   // sweep shallower than the ghost depth K_ is what a partial sweep is)
   int sweep_depth() const { return cond_sweeping() ? Kc_ : K_; }
-  int Kc_ = 0;  // min(K_, deepest tv depth built for the dtype); the CPU backend: K_
+  // min(K_, deepest tv depth built for the dtype in the run's form); the CPU
+  // backend: K_.  Set again wherever the form changes (a source set or cleared).
+  int Kc_ = 0;
+  void set_cond_depth();
   void preflight_extra_field(const char* what, std::size_t extra);
   // copies n values of global row (gi, gj) from column gk on
   using GlobalRows = std::function<void(int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst)>;

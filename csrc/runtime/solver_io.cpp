@@ -662,6 +662,7 @@ void Solver::set_source_rows(const GlobalRows& rows) {
     scatter_global(rows, phys_.dt, l, bufs, 1);
   }
   has_source_ = true;
+  set_cond_depth();
   if (!initialized_) return;  // initialize() times the source forms
   consolidate_fields();
   retune();
@@ -679,6 +680,7 @@ void Solver::clear_source() {
     l.source = nullptr;
   }
   has_source_ = false;
+  set_cond_depth();
   if (!initialized_) return;
   consolidate_fields();
   retune();
@@ -730,6 +732,7 @@ void Solver::set_conductivity_rows(const GlobalRows& rows) {
                      "step is that of the best-conducting material); no conductivity field is set");
   }
   has_cond_ = true;
+  set_cond_depth();
   if (!initialized_) return;
   consolidate_fields();
   retune();
@@ -748,6 +751,7 @@ void Solver::clear_conductivity() {
     l.cond = nullptr;
   }
   has_cond_ = false;
+  set_cond_depth();
   if (!initialized_) return;
   consolidate_fields();
   retune();  // the K-step sweeps are back: timed as at initialize()

@@ -177,6 +177,35 @@ class HeatEquation3D:
         v[-1] = 1.0
         return np.broadcast_to(v[None, :, None], self.n).copy()
 
+    def layered_convective_slab_steady(self, c: np.ndarray, beta: float, ambient: float = 0.0) -> np.ndarray:
+        """Exact steady state of the discrete scheme for a composite wall cooled
+        by a fluid: a conductivity ``c`` that varies in y only (as for
+        ``layered_steady``), x-, x+, z-, z+ insulated, y- convective with
+        coefficient ``beta`` > 0 and ambient ``ambient``, y+ Dirichlet at 1.  With
+        the face weights w_{j+1/2} = 0.5 (c_j + c_{j+1}) a constant flux F passes
+        every y face: beta w_{1/2} (T_1 - T_inf) = F at the wall (its ghost is
+        T_1 + beta (T_inf - T_1), the weight still reads c at the wall vertex),
+        w_{j+1/2} (T_{j+1} - T_j) = F inside, and T_{Ny-1} = 1 fixes F.  Constant
+        in x and z; the y- wall vertices hold the ghost (global array, float64)."""
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"layered_convective_slab_steady: beta {beta} outside (0, 1]")
+        c = np.asarray(c, dtype=np.float64)
+        if c.shape != tuple(self.n):
+            raise ValueError(f"layered_convective_slab_steady: shape {c.shape} != grid {tuple(self.n)}")
+        cy = c[0, :, 0]
+        if not np.array_equal(c, np.broadcast_to(cy[None, :, None], self.n)):
+            raise ValueError("layered_convective_slab_steady: the conductivity must vary in y only")
+        w = 0.5 * (cy[:-1] + cy[1:])  # w[j] = w_{j+1/2}
+        # resistances from T_inf up to vertex j = 1 .. Ny - 1
+        r = np.concatenate(([1.0 / (float(beta) * w[0])], 1.0 / w[1:]))
+        R = np.cumsum(r)
+        F = (1.0 - float(ambient)) / R[-1]
+        v = np.empty(self.n[1], dtype=np.float64)
+        v[1:] = float(ambient) + F * R
+        v[0] = v[1] + float(beta) * (float(ambient) - v[1])
+        v[-1] = 1.0
+        return np.broadcast_to(v[None, :, None], self.n).copy()
+
     def error_percent(self, T: np.ndarray) -> float:
         """100 * mean |T - y| over interior points (the reference's 'L2-norm error')."""
         y = self.steady_state()
@@ -348,7 +377,8 @@ class HeatSolver:
         stable).  A value outside (0, 1] or not finite is the native
         ``UsageError`` (a RuntimeError), raised on every rank.  While set, every
         iteration runs as a single step, or, with ``conductivity_sweeps=True``,
-        in K-step sweeps of the tv kernels (same bits).  Keeps the field, restarts the iteration count and
+        in K-step sweeps of the tv kernels (same bits; behind insulated or
+        convective walls their wall forms).  Keeps the field, restarts the iteration count and
         the convergence state at 0.  Collective."""
         c = np.ascontiguousarray(np.asarray(c, dtype=np.float64))
         if c.shape != tuple(self.model.n):

@@ -158,7 +158,7 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
 
     ``walls``: insulated walls as ``wall_coords`` gives them (CPU tensors only,
-    with or without a source, not with a conductivity: the single-step gfx950
+    with or without a source or a conductivity: the single-step gfx950
     kernels run on wall planes copied from their inward neighbours instead).  ``conv``: the faces
     among them that are convective (``convective_faces`` forms), with the
     ambient temperature ``ambient``.
@@ -272,7 +272,10 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     GPU tensors then run the convective form (stencil_tbl_conv.hip).  ``walls``
     together with ``source``: the wall or convective form with a source
     (stencil_tbl_wall_src.hip / stencil_tbl_conv_src.hip) on GPU tensors, K
-    single steps with both on CPU tensors."""
+    single steps with both on CPU tensors.  ``walls`` together with
+    ``conductivity`` (and a ``tv2`` / ``tv3`` kernel): the wall forms of the tv
+    sweep (stencil_tbv_wall.hip / stencil_tbv_conv.hip, with or without a source)
+    on GPU tensors, K single steps with them on CPU tensors."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
