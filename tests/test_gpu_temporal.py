@@ -112,7 +112,8 @@ VARIANTS_K = {3: ["tl3", "tl3:1:3:1:16:0:4", "tl3:1:2:1:16:0:3", "tl3:1:3:1:16:5
                   "tl4:1:3:1:12:0:3:2", "tl4:1:3:1:12:0:3"],
               2: ["tl2", "tl2:1:2:1:16:0:3", "tl2:1:5:1:16:0:3:2", "tl2:1:5:1:16:0:3:66", "tl2:1:3:1:16:0:3:66"]}
 # fp32: tlK:2:… is the packed-pair lean kernel (stencil_tbp.hip)
-PAIR = {3: ["tl3:2:3:1:16:0:3", "tl3:2:3:1:16:0:3:2", "tl3:2:3:1:16:0:3:66", "tl3:2:3:1:16:0:4", "tl3:2:2:1:16:0:3", "tl3:2:3:1:16:5:3"],
+PAIR = {3: ["tl3:2:3:1:16:0:3", "tl3:2:3:1:16:0:3:2", "tl3:2:3:1:16:0:3:66", "tl3:2:3:1:16:0:4", "tl3:2:2:1:16:0:3", "tl3:2:3:1:16:5:3",
+            "tl3:2:3:1:16:0:3:0", "tl3:2:3:1:16:0:3:3", "tl3:2:3:1:16:0:3:17", "tl3:2:3:1:16:0:3:19"],
         4: ["tl4:2:2:1:16:0:3", "tl4:2:2:1:16:0:4", "tl4:2:2:1:16:7:3", "tl4:2:2:1:16:0:3:64"],
         2: ["tl2:2:2:1:16:0:3", "tl2:2:3:1:16:0:3", "tl2:2:2:1:16:0:3:64"]}
 VARIANTS_K_F32 = PAIR
