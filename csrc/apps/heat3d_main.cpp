@@ -102,6 +102,9 @@ static int drive(const Config& cfg, Solver& solver) {
   RunResult r = solver.run();
   double gerr = 0, lerr = 0;
   solver.compute_error(&gerr, &lerr);
+  HeatBalance hb;
+  if (cfg.heat_balance) hb = solver.heat_balance();  // collective
+  static const char* kFaces[kNumFaces] = {"x-", "x+", "y-", "y+", "z-", "z+"};
   if (root) {
     std::printf("Computational time (parallel): %.6f\n\n", r.seconds);
     if (r.converged)
@@ -123,6 +126,16 @@ static int drive(const Config& cfg, Solver& solver) {
       std::printf("heat3d: phase timing (ms/iteration, synchronised):");
       for (auto& pt : solver.phase_times()) std::printf(" %s=%.4f", pt.first.c_str(), pt.second);
       std::printf("\n");
+    }
+    if (cfg.heat_balance) {
+      std::printf("heat3d: heat balance of the final field (flows positive into the body)\n");
+      std::printf("heat3d:   heat         = %.17g\n", hb.heat);
+      std::printf("heat3d:   t_min        = %.17g\n", hb.t_min);
+      std::printf("heat3d:   t_max        = %.17g\n", hb.t_max);
+      std::printf("heat3d:   nonfinite    = %lld\n", (long long)hb.nonfinite);
+      for (int f = 0; f < kNumFaces; ++f) std::printf("heat3d:   flow %s      = %.17g\n", kFaces[f], hb.flow[f]);
+      std::printf("heat3d:   source_power = %.17g\n", hb.source_power);
+      std::printf("heat3d:   imbalance    = %.17g\n", hb.imbalance);
     }
     if (r.fault) std::fprintf(stderr, "heat3d: non-finite residual detected at iteration %lld\n",
                               (long long)r.conv_iter);
@@ -172,6 +185,18 @@ static int drive(const Config& cfg, Solver& solver) {
     j.set("hip_library", hi.library);
     j.set("rccl_version", rccl_version());
     j.set("rccl_library", rccl_library_path());
+    if (cfg.heat_balance) {
+      io::Json b, fl;
+      b.set("heat", hb.heat);
+      b.set("t_min", hb.t_min);
+      b.set("t_max", hb.t_max);
+      b.set("nonfinite", (int64_t)hb.nonfinite);
+      b.set("source_power", hb.source_power);
+      for (int f = 0; f < kNumFaces; ++f) fl.set(kFaces[f], hb.flow[f]);
+      b.set_raw("flow", fl.dump());
+      b.set("imbalance", hb.imbalance);
+      j.set_raw("heat_balance", b.dump());
+    }
     io::write_file_atomic(cfg.json_out, j.dump() + "\n");
   }
   return r.fault ? 3 : 0;

@@ -208,6 +208,9 @@ std::string Config::usage() {
      << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
      << "  --wall-source-sweeps      with insulated or convective walls and a heat source: K-step sweeps of the\n"
      << "                            wall forms with a source instead of single steps; same bits (not with --compat)\n"
+     << "  --heat-balance            after the run report: stored heat, temperature range, heat flow through each\n"
+     << "                            face (positive into the body), source power and their balance, summed on the\n"
+     << "                            device; also a \"heat_balance\" object in --json-out (not with --compat)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -356,6 +359,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
     else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
+    else if (key == "--heat-balance") c.heat_balance = true;
     else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
     else if (key == "--convective") c.convective = parse_convective(get("--convective"));
     else if (key == "--ambient") {
@@ -490,6 +494,8 @@ Config Config::parse(int argc, const char* const* argv) {
                      insulated_str(convective_mask(c.convective) & c.insulated));
   if (c.cond_sweeps && c.compat)
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
+  if (c.heat_balance && (c.compat || c.scheme == "reference"))
+    throw UsageError("--heat-balance is not part of --compat / --scheme reference (the reference's report)");
   if (c.wall_source_sweeps && c.compat)
     throw UsageError("--wall-source-sweeps is not part of --compat (the reference has neither walls nor a source)");
   return c;

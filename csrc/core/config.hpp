@@ -74,6 +74,10 @@ struct Config {
   // (stencil_tbl_wall_src.hip, stencil_tbl_conv_src.hip) instead of single
   // steps.  Off by default; without walls or without a source it does nothing.
   bool wall_source_sweeps = false;
+  // --heat-balance: after the run report, the heat balance of the final field
+  // (Solver::heat_balance), one line per quantity, and a "heat_balance" object
+  // in --json-out.  Off by default: the output is then unchanged.
+  bool heat_balance = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   // --insulated: faces of the global grid that are zero-flux walls instead of

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../core/common.hpp"
+#include "heat_balance.hpp"
 #include "layout.hpp"
 
 namespace heat3d {
@@ -300,6 +301,16 @@ void error_accumulate(DType t, const void* f, const Layout& L, const Box& box,
                       const int64_t gstart[3], double hy, double* scratch, DeviceState* s,
                       void* stream);
 int64_t error_scratch_elems();
+// The heat balance of one box (heat_balance.hpp; heat_balance.hip): the raw
+// double-double sums, min / max keys and non-finite count of p into *out, or
+// added to *out (accumulate: the next subdomain of the same process, in call
+// order).  One pass over p.box on a fixed grid, per-block partials in
+// `scratch` (balance_scratch_bytes() of device memory), one single-block
+// kernel that combines them in a fixed order: no atomics, the same bits for
+// the same call.  Wall vertices of insulated / convective faces are not read
+// as temperatures.
+void heat_balance(DType t, const BalanceParams& p, void* scratch, BalanceSums* out, bool accumulate, void* stream);
+std::size_t balance_scratch_bytes();
 // Fault injection (tests): write `value` at local owned point (i,j,k).
 void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
           void* stream);
@@ -330,6 +341,10 @@ void error_accumulate(DType t, const void* f, const Layout& L, const Box& box,
                       const int64_t gstart[3], double hy, DeviceState* s);
 void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value);
 unsigned long long box_bitsum(DType t, const void* f, const Layout& L, const Box& b);
+// The definition of the heat balance (heat_balance.hpp): rows of p.box in fixed
+// chunks, each summed in order, the chunks combined in order, so the result
+// does not depend on the thread count.  *out is set, or added to (accumulate).
+void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate);
 }  // namespace cpu
 
 // Shared scalar logic of the convergence check (heat3D.cu:1026-1073 with the

@@ -272,5 +272,85 @@ void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, do
   else static_cast<float*>(f)[L.index(i, j, k)] = static_cast<float>(value);
 }
 
+// ---- heat balance (heat_balance.hpp): the definition ---------------------------
+// Rows (i, j) of the box in chunks of kBalanceChunkRows, each chunk summed in
+// row order and z order by one thread, the chunks combined in chunk order:
+// the same bits for every thread count.
+constexpr int64_t kBalanceChunkRows = 64;
+
+template <typename Real>
+static void balance_chunk(const BalanceParams& p, int64_t r0, int64_t r1, BalanceSums* out) {
+  const Real* T = static_cast<const Real*>(p.field);
+  const Real* S = static_cast<const Real*>(p.src);
+  const Real* Ch = static_cast<const Real*>(p.cond);
+  const Layout& L = p.L;
+  const Box& b = p.box;
+  const int64_t ey = b.extent(1);
+  const int64_t stride[3] = {L.sx, L.sy, 1};
+  const Real tinf = static_cast<Real>(p.ambient);
+  DD acc[kBalanceSums] = {};
+  long long kmin = kBalKeyNone, kmax = ~kBalKeyNone;
+  unsigned long long bad = 0;
+  // one face term of the point at idx (centre c): the neighbour the scheme uses
+  // across face (a, e), times the scheme's face weight
+  auto face = [&](int a, int e, int64_t idx, Real c) {
+    if (p.kind[a][e] == kWallInsulated) return;  // the neighbour is c itself: no flow, exactly
+    const int64_t q = idx + (e ? stride[a] : -stride[a]);
+    const Real n = p.kind[a][e] == kWallDirichlet ? T[q] : convective_ghost<Real>(c, static_cast<Real>(p.beta[a][e]), tinf);
+    const double d = static_cast<double>(n) - static_cast<double>(c);
+    double term = d;
+    if (Ch) {
+      const Real w = Ch[idx] + Ch[q];
+      term = static_cast<double>(w) * d;
+    }
+    dd_add(acc[2 + 2 * a + e], term);
+  };
+  for (int64_t r = r0; r < r1; ++r) {
+    const int64_t i = b.lo[0] + r / ey, j = b.lo[1] + r % ey;
+    const bool xm = i == p.wall[0][0], xp = i == p.wall[0][1], ym = j == p.wall[1][0], yp = j == p.wall[1][1];
+    for (int64_t k = b.lo[2]; k < b.hi[2]; ++k) {
+      const int64_t idx = L.index(i, j, k);
+      const Real c = T[idx];
+      dd_add(acc[0], static_cast<double>(c));
+      bad += bal_nonfinite(c);
+      if (c == c) {
+        const long long key = bal_key(static_cast<double>(c));
+        kmin = key < kmin ? key : kmin;
+        kmax = key > kmax ? key : kmax;
+      }
+      if (S) dd_add(acc[1], static_cast<double>(S[idx]));
+      if (xm) face(0, 0, idx, c);
+      if (xp) face(0, 1, idx, c);
+      if (ym) face(1, 0, idx, c);
+      if (yp) face(1, 1, idx, c);
+      if (k == p.wall[2][0]) face(2, 0, idx, c);
+      if (k == p.wall[2][1]) face(2, 1, idx, c);
+    }
+  }
+  bal_clear(*out);
+  for (int q = 0; q < kBalanceSums; ++q) out->hi[q] = acc[q].hi, out->lo[q] = acc[q].lo;
+  out->kmin = kmin;
+  out->kmax = kmax;
+  out->nonfinite = bad;
+}
+
+void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate) {
+  const Box& b = p.box;
+  const int64_t rows = b.empty() ? 0 : b.extent(0) * b.extent(1);
+  const int64_t chunks = (rows + kBalanceChunkRows - 1) / kBalanceChunkRows;
+  std::vector<BalanceSums> part(static_cast<std::size_t>(chunks));
+#pragma omp parallel for schedule(static) if (omp_worth(b.volume()))
+  for (int64_t ch = 0; ch < chunks; ++ch) {
+    const int64_t r0 = ch * kBalanceChunkRows, r1 = std::min(rows, r0 + kBalanceChunkRows);
+    if (t == DType::F64) balance_chunk<double>(p, r0, r1, &part[ch]);
+    else balance_chunk<float>(p, r0, r1, &part[ch]);
+  }
+  BalanceSums total;
+  bal_clear(total);
+  for (int64_t ch = 0; ch < chunks; ++ch) bal_merge(total, part[ch]);
+  if (accumulate) bal_merge(*out, total);
+  else *out = total;
+}
+
 }  // namespace cpu
 }  // namespace heat3d

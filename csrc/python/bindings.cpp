@@ -144,6 +144,33 @@ void set_conv(StencilParams& p, const std::array<double, 6>& c, double ambient) 
   p.ambient = ambient;
 }
 
+// heat balance of a box on raw pointers: wall = the wall-adjacent coordinate per face (NO_WALL: none in the
+// box), kind = 0 Dirichlet, 1 insulated, 2 convective, beta = the convective coefficients
+BalanceParams bparams(int64_t field_ptr, const std::array<int64_t, 3>& n, int64_t esize, const std::array<int64_t, 3>& g,
+                      const std::array<int64_t, 6>& box, int64_t src_ptr, int64_t cond_ptr,
+                      const std::array<int64_t, 6>& wall, const std::array<int, 6>& kind,
+                      const std::array<double, 6>& beta, double ambient) {
+  BalanceParams p;
+  p.field = reinterpret_cast<const void*>(field_ptr);
+  p.src = reinterpret_cast<const void*>(src_ptr);
+  p.cond = reinterpret_cast<const void*>(cond_ptr);
+  p.L = to_layout(n, esize, g[0], g[1], g[2]);
+  p.box = to_box(box);
+  for (int a = 0; a < 3; ++a) {
+    if (!(0 <= p.box.lo[a] && p.box.lo[a] <= p.box.hi[a] && p.box.hi[a] <= n[a]))
+      throw UsageError("heat_balance: the box lies outside the owned block");
+    for (int e = 0; e < 2; ++e) {
+      const int f = 2 * a + e;
+      if (kind[f] < 0 || kind[f] > 2) throw UsageError("heat_balance: kind is 0 (Dirichlet), 1 (insulated) or 2 (convective)");
+      p.wall[a][e] = wall[f] >= p.box.lo[a] && wall[f] < p.box.hi[a] ? wall[f] : kNoBalanceWall;
+      p.kind[a][e] = kind[f];
+      p.beta[a][e] = beta[f];
+    }
+  }
+  p.ambient = ambient;
+  return p;
+}
+
 StencilParams sparams(int64_t in_ptr, int64_t out_ptr, const std::array<int64_t, 3>& n,
                       int64_t esize, const std::array<int64_t, 6>& box,
                       const std::array<double, 3>& D, int64_t state_ptr, int slot) {
@@ -536,6 +563,9 @@ PYBIND11_MODULE(_heat3d, m) {
   m.attr("RESIDUAL_SLOTS") = (int64_t)kResidualSlots;
   m.attr("STATE_DONE_OFFSET") = (int64_t)offsetof(DeviceState, done);
   m.attr("RESIDUAL_INIT_BITS") = (unsigned long long)kResidualInitBits;
+  // heat balance: the raw result (16 doubles hi[8], lo[8]; int64 min key, max key; uint64 non-finite count)
+  m.attr("BALANCE_SUMS_BYTES") = (int64_t)sizeof(BalanceSums);
+  m.attr("BALANCE_SCRATCH_BYTES") = (int64_t)heat3d::hip::balance_scratch_bytes();
 
   // --- raw kernels (pointers as ints; stream = hipStream_t as int) ----------
   py::module_ hk = m.def_submodule("hip", "gfx950 kernels on device pointers");
@@ -636,6 +666,19 @@ PYBIND11_MODULE(_heat3d, m) {
     hip::bandwidth_probe(kind, reinterpret_cast<const void*>(src), reinterpret_cast<void*>(dst), bytes, blocks,
                          reinterpret_cast<void*>(stream));
   });
+  // the raw sums of the heat balance (kernels/heat_balance.hpp) into out_ptr (BALANCE_SUMS_BYTES of device
+  // memory), scratch_ptr = BALANCE_SCRATCH_BYTES of device memory
+  hk.def("heat_balance", [](const std::string& dt, int64_t field_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                            std::array<int64_t, 6> box, int64_t src_ptr, int64_t cond_ptr, std::array<int64_t, 6> wall,
+                            std::array<int, 6> kind, std::array<double, 6> beta, double ambient, int64_t scratch_ptr,
+                            int64_t out_ptr, bool accumulate, int64_t stream) {
+    DType t = dt_of(dt);
+    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient);
+    hip::heat_balance(t, p, reinterpret_cast<void*>(scratch_ptr), reinterpret_cast<BalanceSums*>(out_ptr), accumulate,
+                      reinterpret_cast<void*>(stream));
+  }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
+     py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("scratch_ptr"),
+     py::arg("out_ptr"), py::arg("accumulate"), py::arg("stream"));
   hk.def("check_convergence", [](int64_t state_ptr, int slot, int64_t stream) {
     hip::check_convergence(reinterpret_cast<DeviceState*>(state_ptr), slot, reinterpret_cast<void*>(stream));
   });
@@ -730,6 +773,17 @@ PYBIND11_MODULE(_heat3d, m) {
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
      py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
+  ck.def("heat_balance", [](const std::string& dt, int64_t field_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                            std::array<int64_t, 6> box, int64_t src_ptr, int64_t cond_ptr, std::array<int64_t, 6> wall,
+                            std::array<int, 6> kind, std::array<double, 6> beta, double ambient, int64_t out_ptr,
+                            bool accumulate) {
+    DType t = dt_of(dt);
+    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient);
+    py::gil_scoped_release nogil;
+    cpu::heat_balance(t, p, reinterpret_cast<BalanceSums*>(out_ptr), accumulate);
+  }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
+     py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("out_ptr"),
+     py::arg("accumulate"));
   ck.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h) {
     DType t = dt_of(dt);
@@ -837,6 +891,24 @@ PYBIND11_MODULE(_heat3d, m) {
         double g = 0, l = 0;
         s.compute_error(&g, &l);
         return py::make_tuple(g, l);
+      })
+      .def("heat_balance", [](Solver& s) {
+        HeatBalance b;
+        {
+          py::gil_scoped_release nogil;
+          b = s.heat_balance();
+        }
+        py::dict d, flow;
+        d["heat"] = b.heat;
+        d["t_min"] = b.t_min;
+        d["t_max"] = b.t_max;
+        d["nonfinite"] = b.nonfinite;
+        d["source_power"] = b.source_power;
+        static const char* faces[kNumFaces] = {"x-", "x+", "y-", "y+", "z-", "z+"};
+        for (int f = 0; f < kNumFaces; ++f) flow[py::str(faces[f])] = b.flow[f];
+        d["flow"] = flow;
+        d["imbalance"] = b.imbalance;
+        return d;
       })
       .def("gather_global", [](Solver& s) -> py::object {
         std::vector<double> v;

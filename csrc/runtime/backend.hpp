@@ -115,6 +115,10 @@ class Backend {
   virtual void error_accumulate(DType t, const void* f, const Layout& L, const Box& box,
                                 const int64_t gstart[3], double hy, DeviceState* st,
                                 StreamId s) = 0;
+  // the heat balance of one box (kernels/heat_balance.hpp) into *out, or added
+  // to it (accumulate); `out` is memory of alloc().  The HIP backend keeps the
+  // kernel's per-block partials in a buffer of its own, allocated on first use.
+  virtual void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate, StreamId s) = 0;
   virtual void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k,
                     double value, StreamId s) = 0;
   // order-independent checksum of a box into *out (device memory on HIP)

@@ -109,6 +109,9 @@ class CpuBackend final : public Backend {
                         const int64_t gstart[3], double hy, DeviceState* st, StreamId) override {
     cpu::error_accumulate(t, f, L, box, gstart, hy, st);
   }
+  void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate, StreamId) override {
+    cpu::heat_balance(t, p, out, accumulate);
+  }
   void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
             StreamId) override {
     cpu::poke(t, f, L, i, j, k, value);

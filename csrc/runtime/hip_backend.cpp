@@ -158,6 +158,7 @@ class HipBackend final : public Backend {
     for (auto& s : caps_)
       if (s) (void)hipStreamDestroy(s);
     if (err_scratch_) (void)hipFree(err_scratch_);
+    if (bal_scratch_) (void)hipFree(bal_scratch_);
     for (auto& s : streams_)
       if (s) (void)hipStreamDestroy(s);
   }
@@ -493,6 +494,10 @@ class HipBackend final : public Backend {
     if (!err_scratch_) err_scratch_ = static_cast<double*>(alloc(sizeof(double) * hip::error_scratch_elems()));
     op(s, [&](hipStream_t q) { hip::error_accumulate(t, f, L, box, gstart, hy, err_scratch_, st, q); });
   }
+  void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate, StreamId s) override {
+    if (!bal_scratch_) bal_scratch_ = alloc(hip::balance_scratch_bytes());
+    op(s, [&](hipStream_t q) { hip::heat_balance(t, p, bal_scratch_, out, accumulate, q); });
+  }
   void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
             StreamId s) override {
     op(s, [&](hipStream_t st) { hip::poke(t, f, L, i, j, k, value, st); });
@@ -597,6 +602,7 @@ class HipBackend final : public Backend {
   int sig_ord_[kNumStreams] = {};
   hipEvent_t fork_ev_ = nullptr, join_ev_[kNumStreams] = {nullptr, nullptr, nullptr};
   double* err_scratch_ = nullptr;
+  void* bal_scratch_ = nullptr;  // heat_balance: per-block partials
   Roctx roctx_;
 };
 

@@ -486,6 +486,7 @@ Solver::~Solver() {
   }
   be_->release(dstate_);
   if (rstate_) be_->release(rstate_);
+  if (bal_out_) be_->release(bal_out_);
   be_->release_host(hstate_);
   comm_.reset();  // communicators before the device
 }
@@ -2475,6 +2476,81 @@ void Solver::compute_error(double* global_mean, double* local_mean) {
   be_->copy(e, base + off, sizeof(e), CopyKind::D2H, kCompute);
   be_->sync(kCompute);
   if (global_mean) *global_mean = e[1] > 0 ? e[0] / e[1] : 0.0;
+}
+
+HeatBalance Solver::heat_balance() {
+  if (cfg_.compat) throw UsageError("the heat balance is not part of --compat (the reference's report)");
+  be_->sync_all();
+  const int p = cur();
+  // the result, and behind it three words for the all-reduces of a multi-process run
+  if (!bal_out_) bal_out_ = static_cast<BalanceSums*>(be_->alloc(sizeof(BalanceSums) + 3 * sizeof(unsigned long long)));
+  const auto& N = dec_.N;
+  for (std::size_t i = 0; i < local_.size(); ++i) {
+    const auto& l = local_[i];
+    BalanceParams bp;
+    bp.field = l.field[p];
+    bp.src = has_source_ ? l.source : nullptr;
+    bp.cond = has_cond_ ? l.cond : nullptr;
+    bp.L = l.L;
+    bp.ambient = cfg_.ambient;
+    for (int a = 0; a < 3; ++a) {
+      // the updated points of this subdomain: global indices 1 .. N - 2
+      bp.box.lo[a] = std::max<int64_t>(l.owned.lo[a], 1 - l.sd.gstart[a]);
+      bp.box.hi[a] = std::min<int64_t>(l.owned.hi[a], N[a] - 1 - l.sd.gstart[a]);
+      for (int e = 0; e < 2; ++e) {
+        const int f = 2 * a + e;
+        const int64_t w = (e ? N[a] - 2 : 1) - l.sd.gstart[a];
+        bp.wall[a][e] = w >= bp.box.lo[a] && w < bp.box.hi[a] ? w : kNoBalanceWall;
+        bp.kind[a][e] = ((conv_ >> f) & 1u) ? kWallConvective : ((walls_ >> f) & 1u) ? kWallInsulated : kWallDirichlet;
+        bp.beta[a][e] = ((conv_ >> f) & 1u) ? conv_beta_[f] : 0.0;
+      }
+    }
+    be_->heat_balance(dt_, bp, bal_out_, i > 0, kCompute);
+  }
+  BalanceSums h;
+  bal_clear(h);
+  if (!local_.empty()) be_->copy(&h, bal_out_, sizeof(h), CopyKind::D2H, kCompute);
+  be_->sync(kCompute);
+  unsigned long long bad = h.nonfinite;
+  if (!comm_->all_local() && comm_->size() > 1) {
+    // the plain pair all-reduce: hi and lo summed apart, renormalised below;
+    // min / max as biased keys under an unsigned max
+    const unsigned long long bias = 1ull << 63;
+    // ... and the count under an integer sum, in the three words behind the result
+    unsigned long long mm[3] = {(unsigned long long)h.kmax ^ bias, ~((unsigned long long)h.kmin ^ bias), bad};
+    unsigned long long* d = reinterpret_cast<unsigned long long*>(bal_out_ + 1);
+    be_->copy(d, mm, sizeof(mm), CopyKind::H2D, kCompute);
+    comm_->allreduce(bal_out_, 2 * kBalanceSums, RedType::F64, RedOp::Sum, *be_, kCompute);
+    comm_->allreduce(d, 2, RedType::U64, RedOp::Max, *be_, kCompute);
+    comm_->allreduce(d + 2, 1, RedType::U64, RedOp::Sum, *be_, kCompute);
+    be_->copy(&h, bal_out_, sizeof(h), CopyKind::D2H, kCompute);
+    be_->copy(mm, d, sizeof(mm), CopyKind::D2H, kCompute);
+    be_->sync(kCompute);
+    h.kmax = (long long)(mm[0] ^ bias);
+    h.kmin = (long long)(~mm[1] ^ bias);
+    bad = mm[2];
+  }
+  double sum[kBalanceSums];
+  for (int q = 0; q < kBalanceSums; ++q) sum[q] = h.hi[q] + h.lo[q];  // the final rounding
+  HeatBalance r;
+  const double* hh = phys_.h;
+  const double vol = hh[0] * hh[1] * hh[2];
+  r.heat = vol * sum[0];
+  r.t_min = bal_unkey(h.kmin);
+  r.t_max = bal_unkey(h.kmax);
+  r.nonfinite = (int64_t)bad;
+  r.source_power = has_source_ ? vol / phys_.dt * sum[1] : 0.0;
+  double total = 0.0;
+  for (int a = 0; a < 3; ++a)
+    for (int e = 0; e < 2; ++e) {
+      const int b = (a + 1) % 3, c = (a + 2) % 3;
+      const bool wall = ((walls_ >> (2 * a + e)) & 1u) && !((conv_ >> (2 * a + e)) & 1u);
+      // an insulated face: exactly 0.0 (no term is formed)
+      r.flow[2 * a + e] = wall ? 0.0 : phys_.alpha * hh[b] * hh[c] / hh[a] * sum[2 + 2 * a + e];
+      total += r.flow[2 * a + e];
+    }
+  r.imbalance = total + r.source_power;
+  return r;
 }
 
 int Solver::verify_halos() {

@@ -56,6 +56,15 @@ struct RunResult {
   double glups = 0.0;        // updated interior points x iterations / s (whole job)
 };
 
+struct HeatBalance {
+  double heat = 0.0;          // hx hy hz * sum of T over the updated points
+  double t_min = 0.0, t_max = 0.0;  // over the non-NaN values (NaN: there is none)
+  int64_t nonfinite = 0;      // NaN or Inf values among them
+  double source_power = 0.0;  // hx hy hz / dt * sum of S (0 without a source)
+  double flow[6] = {0, 0, 0, 0, 0, 0};  // x-, x+, y-, y+, z-, z+; positive: into the body
+  double imbalance = 0.0;     // sum of the flows + source_power = d(heat)/dt of the scheme
+};
+
 struct HostState {
   double norm, eps, last_residual, error_sum, error_count;
   int64_t iter, conv_iter;
@@ -174,6 +183,17 @@ class Solver {
   // against T = y: only meaningful for the reference problem (no source, the
   // default walls).
   void compute_error(double* global_mean, double* local_mean);
+
+  // Heat balance of the current field (docs/ARCHITECTURE.md "Heat balance"):
+  // stored heat, temperature range and non-finite count over the updated
+  // points, the heat flow through each face (positive into the body), the
+  // source power, and their sum, the rate of change of the stored heat that the
+  // scheme applies at this instant.  Summed on the device in double-double on a
+  // fixed reduction shape (the same call returns the same bits), the local
+  // subdomains in order; across processes an all-reduce of the (hi, lo) pairs.
+  // Synchronises first; collective; the same result on every rank.  Not with
+  // --compat (UsageError).
+  HeatBalance heat_balance();
 
   // Field access.  gather_global fills `out` (N0*N1*N2 values as double,
   // z fastest) on the root process only; returns false elsewhere.
@@ -496,6 +516,7 @@ class Solver {
 
   DeviceState* dstate_ = nullptr;   // device
   DeviceState* rstate_ = nullptr;   // device scratch of resolve_coarse (allocated on first use)
+  BalanceSums* bal_out_ = nullptr;  // device result of heat_balance (allocated on first use)
   DeviceState* hstate_ = nullptr;   // pinned host mirror
   int64_t issued_ = 0;              // iterations enqueued so far (absolute index)
   int cur_ = 0;               // buffer holding T^{issued_}

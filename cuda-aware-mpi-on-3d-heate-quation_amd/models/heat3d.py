@@ -153,6 +153,20 @@ class HeatEquation3D:
         v[-1] = 1.0
         return np.broadcast_to(v[None, :, None], self.n).copy()
 
+    def convective_slab_flows(self, beta: float, ambient: float = 0.0) -> Dict[str, float]:
+        """Exact heat flows (``HeatSolver.heat_balance()["flow"]``, positive into the
+        body) of the slab steady state ``convective_slab_steady``: the constant
+        flux s per face passes every y face, so -alpha hx hz / hy * s per point
+        of a y plane, (Nx - 2)(Nz - 2) of them, leaves through y- and the opposite
+        value enters through y+; the four insulated faces carry none."""
+        if not 0.0 < beta <= 1.0:
+            raise ValueError(f"convective_slab_flows: beta {beta} outside (0, 1]")
+        Nx, Ny, Nz = self.n
+        h = self.h
+        s = (1.0 - ambient) / (1.0 / beta + Ny - 2)
+        out = -self.alpha * h[0] * h[2] / h[1] * s * ((Nx - 2) * (Nz - 2))
+        return {"x-": 0.0, "x+": 0.0, "y-": out, "y+": -out, "z-": 0.0, "z+": 0.0}
+
     def convective_slab_source_steady(self, beta: float, ambient: float, q: float) -> np.ndarray:
         """Exact steady state of the discrete scheme for the slab problem of
         ``convective_slab_steady`` with a uniform heat source ``q``.  With
@@ -424,6 +438,21 @@ class HeatSolver:
     def error_percent(self) -> Tuple[float, float]:
         g, loc = self._s.compute_error()
         return 100.0 * g, 100.0 * loc
+
+    def heat_balance(self) -> Dict:
+        """Where the heat is and where it goes, summed on the device over the
+        updated points (global indices 1 .. N - 2) of the current field: ``heat``
+        (hx hy hz sum T), ``t_min`` / ``t_max`` (NaNs ignored), ``nonfinite`` (the
+        count of NaN / Inf values), ``flow`` per face ``{"x-": ..., ...}`` (positive:
+        into the body; exactly 0.0 on an insulated face), ``source_power`` and
+        ``imbalance``, the sum of the flows and the source power: the rate of
+        change of ``heat`` that the scheme applies at this instant.  Every sum is
+        accumulated in double-double on a fixed reduction shape: a repeated
+        call returns the same bits, and decompositions of one process agree to
+        the last rounding (docs/ARCHITECTURE.md, "Heat balance").  Synchronises;
+        collective; the same dict on every rank."""
+        self._ensure()
+        return dict(self._s.heat_balance())
 
     def write_tecplot(self, path: str = "output/out.dat", layout: str = "auto") -> None:
         self._s.write_tecplot(path, layout)

@@ -294,6 +294,94 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
         native().cpu.stencil_sweep3(*args, qptr, cptr, w, convective_faces(conv), float(ambient))
 
 
+def _face_scale(physics, axis: int) -> float:
+    """alpha h_b h_c / h_a, the factor between a face's sum of w (n - c) and its
+    heat flow, evaluated left to right with b, c the two axes after ``axis`` in
+    cyclic order (the one expression every backend and the reference use)."""
+    h, alpha = _physics(physics)[:2]
+    b, c = (axis + 1) % 3, (axis + 2) % 3
+    return alpha * h[b] * h[c] / h[axis]
+
+
+def _physics(physics):
+    """(h, alpha, dt) of a ``HeatEquation3D``-like object or of a dict with the
+    keys "h" and "dt" (``native().physics(...)``, ``Solver.physics``; alpha 1)."""
+    if hasattr(physics, "h") and hasattr(physics, "dt"):
+        return tuple(physics.h), float(getattr(physics, "alpha", 1.0)), float(physics.dt)
+    return tuple(physics["h"]), float(physics.get("alpha", 1.0)), float(physics["dt"])
+
+
+def _unkey(k: int) -> float:
+    """The float64 of an ordered key of the native heat balance (heat_balance.hpp bal_key)."""
+    import struct
+
+    if k < 0:
+        k ^= 0x7FFFFFFFFFFFFFFF
+    return struct.unpack("<d", struct.pack("<q", k))[0]
+
+
+def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = None,
+                 source: Optional[PaddedField] = None, cond: Optional[PaddedField] = None,
+                 walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> dict:
+    """Heat balance of ``box`` (default: all owned points) of a field whose block
+    is the interior of its grid: every face of the box lies next to a wall.
+
+    ``physics``: the grid's ``HeatEquation3D`` (or a dict with "h" and "dt").
+    ``walls``: the insulated and convective faces as ``wall_coords`` gives them
+    (the other faces are Dirichlet: the neighbour across them is the stored
+    vertex outside the box); ``conv``: the convective ones among them
+    (``convective_faces`` forms) with the ambient temperature ``ambient``.
+    ``source``: S = dtype(dt q), ``cond``: Ch = dtype(0.5 c), in the field's layout.
+
+    GPU tensors run the gfx950 kernel (heat_balance.hip) on torch's current
+    stream, CPU tensors the definition (cpu::heat_balance).  Returns the dict of
+    ``HeatSolver.heat_balance``.  The wall vertices of insulated and convective
+    faces, and everything else outside the box and its Dirichlet wall vertices,
+    are never read from the field."""
+    ext = native()
+    n = field.n
+    b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
+    w = list(walls) if walls is not None else [ext.NO_WALL] * 6
+    beta = convective_faces(conv)
+    wall, kind = [], []
+    for f in range(6):
+        a, e = divmod(f, 2)
+        if w[f] != ext.NO_WALL:
+            wall.append(int(w[f]))
+            kind.append(2 if beta[f] >= 0 else 1)
+        else:
+            if beta[f] >= 0:
+                raise ValueError("a convective face needs its wall coordinate")
+            wall.append(b[2 * a + 1] - 1 if e else b[2 * a])
+            kind.append(0)
+    beta = [max(v, 0.0) for v in beta]
+    qptr = _source_ptr(field, source)
+    cptr = _cond_ptr(field, cond)
+    out = torch.zeros(ext.BALANCE_SUMS_BYTES // 8, dtype=torch.int64, device=field.device)
+    args = (field.dt, field.data_ptr(), list(n), [field.gx, field.gy, field.gz], b, qptr, cptr, wall, kind, beta,
+            float(ambient))
+    if field.device.type == "cuda":
+        scratch = torch.empty(ext.BALANCE_SCRATCH_BYTES // 8, dtype=torch.int64, device=field.device)
+        ext.hip.heat_balance(*args, scratch.data_ptr(), out.data_ptr(), False, _stream_ptr(field.flat))
+        raw = out.cpu()
+    else:
+        ext.cpu.heat_balance(*args, out.data_ptr(), False)
+        raw = out
+    hi, lo = raw[:8].view(torch.float64), raw[8:16].view(torch.float64)
+    sums = [float(hi[q]) + float(lo[q]) for q in range(8)]  # the final rounding
+    h, alpha, dt = _physics(physics)
+    vol = h[0] * h[1] * h[2]
+    flow = {}
+    total = 0.0
+    for f, name in enumerate(FACES):
+        flow[name] = 0.0 if kind[f] == 1 else _face_scale(physics, f // 2) * sums[2 + f]
+        total += flow[name]
+    source_power = vol / dt * sums[1] if source is not None else 0.0
+    return {"heat": vol * sums[0], "t_min": _unkey(int(raw[16])), "t_max": _unkey(int(raw[17])),
+            "nonfinite": int(raw[18]), "source_power": source_power, "flow": flow,
+            "imbalance": total + source_power}
+
+
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
     """Analytic IC/BC into the padded field (reference heat3D.cu:408-453)."""
     ext = native()
