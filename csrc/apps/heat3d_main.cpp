@@ -99,7 +99,23 @@ static int drive(const Config& cfg, Solver& solver) {
   }
   solver.initialize();
   if (!cfg.initial_file.empty()) solver.set_field_file(cfg.initial_file);
-  RunResult r = solver.run();
+  RunResult r;
+  SteadyResult sr;
+  if (cfg.steady_solve) {
+    // EPS is the relative tolerance, ITER_MAX caps the CG iterations (collective)
+    try {
+      sr = solver.solve_steady(cfg.eps, cfg.iter_max);
+    } catch (const UsageError& e) {
+      if (root) {
+        std::cout << Config::usage() << std::flush;
+        std::cerr << "heat3d: " << e.what() << std::endl;
+      }
+      return 1;
+    }
+    r.seconds = sr.seconds;
+  } else {
+    r = solver.run();
+  }
   double gerr = 0, lerr = 0;
   solver.compute_error(&gerr, &lerr);
   HeatBalance hb;
@@ -107,13 +123,20 @@ static int drive(const Config& cfg, Solver& solver) {
   static const char* kFaces[kNumFaces] = {"x-", "x+", "y-", "y+", "z-", "z+"};
   if (root) {
     std::printf("Computational time (parallel): %.6f\n\n", r.seconds);
-    if (r.converged)
+    if (cfg.steady_solve) {
+      static const char* kStatus[] = {"running", "converged", "max_iter", "breakdown"};
+      std::printf("Steady solve (conjugate gradients) %s in %lld iterations with a relative tolerance of %e\n",
+                  sr.converged ? "has converged" : "did not converge", (long long)sr.iterations, cfg.eps);
+      std::printf("heat3d: steady solve: status=%s restarts=%d residual=%.6e true_residual=%.6e r0_norm=%.6e\n",
+                  kStatus[sr.status >= 0 && sr.status < 4 ? sr.status : 0], sr.restarts, sr.residual,
+                  sr.true_residual, sr.r0_norm);
+    } else if (r.converged)
       std::printf("Simulation has converged in %lld iterations with a convergence threshold of %e\n",
                   (long long)r.conv_iter, cfg.eps);
     else
       std::printf("Simulation did not converge within %lld iterations.\n", (long long)cfg.iter_max);
     std::printf("L2-norm error: %.4f %%\n", 100.0 * (cfg.compat ? lerr : gerr));
-    if (!cfg.compat) {
+    if (!cfg.compat && !cfg.steady_solve) {
       const auto& d = solver.decomposition();
       std::printf("heat3d: backend=%s comm=%s ranks=%d dims=%dx%dx%d dtype=%s kernel=%s "
                   "iterations=%lld issued=%lld GLUPS=%.3f eff_TBps=%.3f norm=%.6e last_residual=%.6e\n",
@@ -185,6 +208,20 @@ static int drive(const Config& cfg, Solver& solver) {
     j.set("hip_library", hi.library);
     j.set("rccl_version", rccl_version());
     j.set("rccl_library", rccl_library_path());
+    if (cfg.steady_solve) {
+      static const char* kStatus[] = {"running", "converged", "max_iter", "breakdown"};
+      io::Json s;
+      s.set_bool("converged", sr.converged);
+      s.set("iterations", (int64_t)sr.iterations);
+      s.set("residual", sr.residual);
+      s.set("true_residual", sr.true_residual);
+      s.set("r0_norm", sr.r0_norm);
+      s.set("seconds", sr.seconds);
+      s.set("restarts", (int64_t)sr.restarts);
+      s.set("status", std::string(kStatus[sr.status >= 0 && sr.status < 4 ? sr.status : 0]));
+      s.set("tol", cfg.eps);
+      j.set_raw("steady_solve", s.dump());
+    }
     if (cfg.heat_balance) {
       io::Json b, fl;
       b.set("heat", hb.heat);

@@ -211,6 +211,11 @@ std::string Config::usage() {
      << "  --heat-balance            after the run report: stored heat, temperature range, heat flow through each\n"
      << "                            face (positive into the body), source power and their balance, summed on the\n"
      << "                            device; also a \"heat_balance\" object in --json-out (not with --compat)\n"
+     << "  --steady-solve            solve for the steady state directly instead of stepping in time: conjugate\n"
+     << "                            gradients on the device from the initial field; EPS is the relative tolerance\n"
+     << "                            of the residual's 2-norm, ITER_MAX caps the iterations; a \"steady_solve\"\n"
+     << "                            object in --json-out (fp64 only; not with --compat; needs a Dirichlet face or\n"
+     << "                            a convective face with a positive coefficient)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -360,6 +365,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
     else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
     else if (key == "--heat-balance") c.heat_balance = true;
+    else if (key == "--steady-solve") c.steady_solve = true;
     else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
     else if (key == "--convective") c.convective = parse_convective(get("--convective"));
     else if (key == "--ambient") {
@@ -496,6 +502,21 @@ Config Config::parse(int argc, const char* const* argv) {
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
   if (c.heat_balance && (c.compat || c.scheme == "reference"))
     throw UsageError("--heat-balance is not part of --compat / --scheme reference (the reference's report)");
+  if (c.steady_solve) {
+    if (c.compat || c.scheme == "reference")
+      throw UsageError("--steady-solve is not part of --compat / --scheme reference (the reference only steps in time)");
+    if (c.dtype != DType::F64)
+      throw UsageError("--steady-solve needs --dtype fp64: in fp32 conjugate gradients cannot get below about "
+                       "kappa * 2^-24 (kappa ~ 4e5 at 1024^3)");
+    if (!(c.eps > 0.0))
+      throw UsageError("--steady-solve: EPS is the relative tolerance and must be positive");
+    bool anchored = false;
+    for (int f = 0; f < kNumFaces; ++f)
+      anchored |= c.convective[f] > 0.0 || (c.convective[f] < 0.0 && !((c.insulated >> f) & 1u));
+    if (!anchored)
+      throw UsageError("--steady-solve needs a Dirichlet face or a convective face with a positive coefficient: "
+                       "with every face insulated the system is singular");
+  }
   if (c.wall_source_sweeps && c.compat)
     throw UsageError("--wall-source-sweeps is not part of --compat (the reference has neither walls nor a source)");
   return c;

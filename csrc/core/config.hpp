@@ -78,6 +78,10 @@ struct Config {
   // (Solver::heat_balance), one line per quantity, and a "heat_balance" object
   // in --json-out.  Off by default: the output is then unchanged.
   bool heat_balance = false;
+  // --steady-solve: instead of the time loop, Solver::solve_steady from the
+  // initial field: EPS is the relative tolerance of the residual's 2-norm,
+  // ITER_MAX caps the CG iterations; a "steady_solve" object in --json-out.
+  bool steady_solve = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   // --insulated: faces of the global grid that are zero-flux walls instead of

@@ -15,6 +15,7 @@
 #include "../core/common.hpp"
 #include "heat_balance.hpp"
 #include "layout.hpp"
+#include "steady_cg.hpp"
 
 namespace heat3d {
 
@@ -311,6 +312,18 @@ int64_t error_scratch_elems();
 // as temperatures.
 void heat_balance(DType t, const BalanceParams& p, void* scratch, BalanceSums* out, bool accumulate, void* stream);
 std::size_t balance_scratch_bytes();
+// The steady solve's three operations (steady_cg.hpp; steady_cg.hip), fp64:
+// q = A p (or r = b - A T) with its dot product, x += alpha p / r -= alpha q
+// with r . r, p = r + beta p.  The dot products go through per-block partials
+// in `scratch` (steady_scratch_bytes() of device memory) and a single-block
+// kernel that combines them in a fixed order into out[0..1] = (hi, lo), or adds
+// them to it (accumulate: the next subdomain of the same process).  No atomics,
+// no scratch memory.  steady_scalars runs steady_scalars_step on the device.
+void steady_apply(DType t, const SteadyApplyParams& p, void* scratch, double* out, bool accumulate, void* stream);
+void steady_update(DType t, const SteadyUpdateParams& p, void* scratch, double* out, bool accumulate, void* stream);
+void steady_direction(DType t, const SteadyDirectionParams& p, void* stream);
+void steady_scalars(SteadyState* st, int phase, void* stream);
+std::size_t steady_scratch_bytes();
 // Fault injection (tests): write `value` at local owned point (i,j,k).
 void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
           void* stream);
@@ -345,6 +358,12 @@ unsigned long long box_bitsum(DType t, const void* f, const Layout& L, const Box
 // chunks, each summed in order, the chunks combined in order, so the result
 // does not depend on the thread count.  *out is set, or added to (accumulate).
 void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate);
+// The definitions of the steady solve's operations (steady_cg_cpu.cpp): rows of
+// the box in the fixed chunks of cpu::heat_balance, each summed in order, the
+// chunks combined in order: the same bits for every thread count.
+void steady_apply(DType t, const SteadyApplyParams& p, double* out, bool accumulate);
+void steady_update(DType t, const SteadyUpdateParams& p, double* out, bool accumulate);
+void steady_direction(DType t, const SteadyDirectionParams& p);
 }  // namespace cpu
 
 // Shared scalar logic of the convergence check (heat3D.cu:1026-1073 with the
@@ -432,6 +451,44 @@ H3D_HD inline Real ftcs_update_var_src(Real c, Real xm, Real xp, Real ym, Real y
                                        Real Dz, Real S) {
   return add_source<Real>(
       ftcs_update_var<Real>(c, xm, xp, ym, yp, zm, zp, hc, hxm, hxp, hym, hyp, hzm, hzp, Dx, Dy, Dz), S);
+}
+
+// ---- the steady solve (steady_cg.hpp) -----------------------------------------
+// The increment of one step, G(T) - T without the source: the update's fused
+// chain started from zero instead of from c, so the low bits that forming G(T)
+// and subtracting c would round away are kept.  A p is its negation on the
+// homogeneous problem, the residual b - A T the increment itself (plus S).
+template <typename Real>
+H3D_HD inline Real steady_increment(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real Dx, Real Dy,
+                                    Real Dz) {
+  const Real ax = h3d_fma(Real(-2), c, xp) + xm;
+  const Real ay = h3d_fma(Real(-2), c, yp) + ym;
+  const Real az = h3d_fma(Real(-2), c, zp) + zm;
+  return h3d_fma(Dz, az, h3d_fma(Dy, ay, Dx * ax));
+}
+// the same with a conductivity (ftcs_update_var's fluxes and face weights)
+template <typename Real>
+H3D_HD inline Real steady_increment_var(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real hc,
+                                        Real hxm, Real hxp, Real hym, Real hyp, Real hzm, Real hzp, Real Dx, Real Dy,
+                                        Real Dz) {
+  const Real fx = var_flux<Real>(c, xm, xp, hc + hxm, hc + hxp);
+  const Real fy = var_flux<Real>(c, ym, yp, hc + hym, hc + hyp);
+  const Real fz = var_flux<Real>(c, zm, zp, hc + hzm, hc + hzp);
+  return h3d_fma(Dz, fz, h3d_fma(Dy, fy, Dx * fx));
+}
+// The neighbour of c across a wall of the global grid (cpu_rows.cpp's ghost
+// rules): an insulated face shows the centre value, a convective one its ghost
+// (towards ambient 0 in A), a Dirichlet one the stored wall value (0 in A).
+template <typename Real>
+H3D_HD inline Real steady_wall_neighbour(int kind, bool residual, Real c, Real stored, Real beta, Real ambient) {
+  if (kind == kWallInsulated) return c;
+  if (kind == kWallConvective) return convective_ghost<Real>(c, beta, residual ? ambient : Real(0));
+  return residual ? stored : Real(0);
+}
+// y <- a x + y, one fused multiply-add (x += alpha p, r -= alpha q, p = r + beta p)
+template <typename Real>
+H3D_HD inline Real steady_axpy(Real a, Real x, Real y) {
+  return h3d_fma(a, x, y);
 }
 
 // Residual term of one point, |T^{n+1} - T^n|, taken in the field's

@@ -171,6 +171,56 @@ BalanceParams bparams(int64_t field_ptr, const std::array<int64_t, 3>& n, int64_
   return p;
 }
 
+// the steady solve's q = A p / r = b - A T of a box on raw pointers (fp64): wall, kind, beta as bparams
+SteadyApplyParams steady_aparams(int64_t in_ptr, int64_t out_ptr, const std::array<int64_t, 3>& n,
+                                 const std::array<int64_t, 3>& g, const std::array<int64_t, 6>& box,
+                                 const std::array<double, 3>& D, int64_t src_ptr, int64_t cond_ptr,
+                                 const std::array<int64_t, 6>& wall, const std::array<int, 6>& kind,
+                                 const std::array<double, 6>& beta, double ambient, bool residual) {
+  SteadyApplyParams p;
+  p.in = reinterpret_cast<const void*>(in_ptr);
+  p.out = reinterpret_cast<void*>(out_ptr);
+  p.src = reinterpret_cast<const void*>(src_ptr);
+  p.cond = reinterpret_cast<const void*>(cond_ptr);
+  p.L = to_layout(n, 8, g[0], g[1], g[2]);
+  p.box = to_box(box);
+  for (int a = 0; a < 3; ++a) {
+    p.D[a] = D[a];
+    for (int e = 0; e < 2; ++e) {
+      const int f = 2 * a + e;
+      if (kind[f] < 0 || kind[f] > 2) throw UsageError("steady_apply: kind is 0 (Dirichlet), 1 (insulated) or 2 (convective)");
+      p.wall[a][e] = wall[f] >= p.box.lo[a] && wall[f] < p.box.hi[a] ? wall[f] : kNoBalanceWall;
+      p.kind[a][e] = kind[f];
+      p.beta[a][e] = beta[f];
+    }
+  }
+  p.ambient = ambient;
+  p.residual = residual;
+  return p;
+}
+SteadyUpdateParams steady_uparams(int64_t x, int64_t p_ptr, int64_t r, int64_t q, const std::array<int64_t, 3>& n,
+                                  const std::array<int64_t, 3>& g, const std::array<int64_t, 6>& box, double alpha) {
+  SteadyUpdateParams p;
+  p.x = reinterpret_cast<void*>(x);
+  p.p = reinterpret_cast<const void*>(p_ptr);
+  p.r = reinterpret_cast<void*>(r);
+  p.q = reinterpret_cast<const void*>(q);
+  p.L = to_layout(n, 8, g[0], g[1], g[2]);
+  p.box = to_box(box);
+  p.alpha = alpha;
+  return p;
+}
+SteadyDirectionParams steady_dparams(int64_t p_ptr, int64_t r, const std::array<int64_t, 3>& n,
+                                     const std::array<int64_t, 3>& g, const std::array<int64_t, 6>& box, double beta) {
+  SteadyDirectionParams p;
+  p.p = reinterpret_cast<void*>(p_ptr);
+  p.r = reinterpret_cast<const void*>(r);
+  p.L = to_layout(n, 8, g[0], g[1], g[2]);
+  p.box = to_box(box);
+  p.beta = beta;
+  return p;
+}
+
 StencilParams sparams(int64_t in_ptr, int64_t out_ptr, const std::array<int64_t, 3>& n,
                       int64_t esize, const std::array<int64_t, 6>& box,
                       const std::array<double, 3>& D, int64_t state_ptr, int slot) {
@@ -566,6 +616,7 @@ PYBIND11_MODULE(_heat3d, m) {
   // heat balance: the raw result (16 doubles hi[8], lo[8]; int64 min key, max key; uint64 non-finite count)
   m.attr("BALANCE_SUMS_BYTES") = (int64_t)sizeof(BalanceSums);
   m.attr("BALANCE_SCRATCH_BYTES") = (int64_t)heat3d::hip::balance_scratch_bytes();
+  m.attr("STEADY_SCRATCH_BYTES") = (int64_t)heat3d::hip::steady_scratch_bytes();
 
   // --- raw kernels (pointers as ints; stream = hipStream_t as int) ----------
   py::module_ hk = m.def_submodule("hip", "gfx950 kernels on device pointers");
@@ -679,6 +730,26 @@ PYBIND11_MODULE(_heat3d, m) {
   }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
      py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("scratch_ptr"),
      py::arg("out_ptr"), py::arg("accumulate"), py::arg("stream"));
+  // the steady solve's operations (kernels/steady_cg.hpp), fp64: out_ptr = 2 doubles (hi, lo) of device
+  // memory, scratch_ptr = STEADY_SCRATCH_BYTES of device memory
+  hk.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                            std::array<int64_t, 6> box, std::array<double, 3> D, int64_t src_ptr, int64_t cond_ptr,
+                            std::array<int64_t, 6> wall, std::array<int, 6> kind, std::array<double, 6> beta,
+                            double ambient, bool residual, int64_t scratch_ptr, int64_t dot_ptr, int64_t stream) {
+    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta, ambient, residual);
+    hip::steady_apply(DType::F64, p, reinterpret_cast<void*>(scratch_ptr), reinterpret_cast<double*>(dot_ptr), false,
+                      reinterpret_cast<void*>(stream));
+  });
+  hk.def("steady_update", [](int64_t x, int64_t p_ptr, int64_t r, int64_t q, std::array<int64_t, 3> n,
+                             std::array<int64_t, 3> g, std::array<int64_t, 6> box, double alpha, int64_t scratch_ptr,
+                             int64_t dot_ptr, int64_t stream) {
+    hip::steady_update(DType::F64, steady_uparams(x, p_ptr, r, q, n, g, box, alpha), reinterpret_cast<void*>(scratch_ptr),
+                       reinterpret_cast<double*>(dot_ptr), false, reinterpret_cast<void*>(stream));
+  });
+  hk.def("steady_direction", [](int64_t p_ptr, int64_t r, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                                std::array<int64_t, 6> box, double beta, int64_t stream) {
+    hip::steady_direction(DType::F64, steady_dparams(p_ptr, r, n, g, box, beta), reinterpret_cast<void*>(stream));
+  });
   hk.def("check_convergence", [](int64_t state_ptr, int slot, int64_t stream) {
     hip::check_convergence(reinterpret_cast<DeviceState*>(state_ptr), slot, reinterpret_cast<void*>(stream));
   });
@@ -784,6 +855,24 @@ PYBIND11_MODULE(_heat3d, m) {
   }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
      py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("out_ptr"),
      py::arg("accumulate"));
+  ck.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                            std::array<int64_t, 6> box, std::array<double, 3> D, int64_t src_ptr, int64_t cond_ptr,
+                            std::array<int64_t, 6> wall, std::array<int, 6> kind, std::array<double, 6> beta,
+                            double ambient, bool residual, int64_t dot_ptr) {
+    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta, ambient, residual);
+    py::gil_scoped_release nogil;
+    cpu::steady_apply(DType::F64, p, reinterpret_cast<double*>(dot_ptr), false);
+  });
+  ck.def("steady_update", [](int64_t x, int64_t p_ptr, int64_t r, int64_t q, std::array<int64_t, 3> n,
+                             std::array<int64_t, 3> g, std::array<int64_t, 6> box, double alpha, int64_t dot_ptr) {
+    py::gil_scoped_release nogil;
+    cpu::steady_update(DType::F64, steady_uparams(x, p_ptr, r, q, n, g, box, alpha), reinterpret_cast<double*>(dot_ptr), false);
+  });
+  ck.def("steady_direction", [](int64_t p_ptr, int64_t r, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
+                                std::array<int64_t, 6> box, double beta) {
+    py::gil_scoped_release nogil;
+    cpu::steady_direction(DType::F64, steady_dparams(p_ptr, r, n, g, box, beta));
+  });
   ck.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h) {
     DType t = dt_of(dt);
@@ -910,6 +999,24 @@ PYBIND11_MODULE(_heat3d, m) {
         d["imbalance"] = b.imbalance;
         return d;
       })
+      .def("solve_steady", [](Solver& s, double tol, int64_t max_iter) {
+        SteadyResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = s.solve_steady(tol, max_iter);
+        }
+        py::dict d;
+        d["converged"] = r.converged;
+        d["iterations"] = r.iterations;
+        d["residual"] = r.residual;
+        d["true_residual"] = r.true_residual;
+        d["r0_norm"] = r.r0_norm;
+        d["seconds"] = r.seconds;
+        d["restarts"] = r.restarts;
+        static const char* status[] = {"running", "converged", "max_iter", "breakdown"};
+        d["status"] = status[r.status >= 0 && r.status < 4 ? r.status : 0];
+        return d;
+      }, py::arg("tol") = 1e-8, py::arg("max_iter") = 0)
       .def("gather_global", [](Solver& s) -> py::object {
         std::vector<double> v;
         bool root;

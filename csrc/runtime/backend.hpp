@@ -119,6 +119,16 @@ class Backend {
   // to it (accumulate); `out` is memory of alloc().  The HIP backend keeps the
   // kernel's per-block partials in a buffer of its own, allocated on first use.
   virtual void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate, StreamId s) = 0;
+  // The steady solve's operations (kernels/steady_cg.hpp), fp64: q = A p or
+  // r = b - A T with its dot product, the update with r . r, the new direction.
+  // out[0..1] = the (hi, lo) sum, set or added to (accumulate); `out` and the
+  // states the parameters name are memory of alloc().  The HIP backend keeps
+  // the per-block partials in a buffer of its own, allocated on first use.
+  virtual void steady_apply(const SteadyApplyParams& p, double* out, bool accumulate, StreamId s) = 0;
+  virtual void steady_update(const SteadyUpdateParams& p, double* out, bool accumulate, StreamId s) = 0;
+  virtual void steady_direction(const SteadyDirectionParams& p, StreamId s) = 0;
+  // steady_scalars_step on the state, in stream order
+  virtual void steady_scalars(SteadyState* st, int phase, StreamId s) = 0;
   virtual void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k,
                     double value, StreamId s) = 0;
   // order-independent checksum of a box into *out (device memory on HIP)

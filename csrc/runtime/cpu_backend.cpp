@@ -112,6 +112,14 @@ class CpuBackend final : public Backend {
   void heat_balance(DType t, const BalanceParams& p, BalanceSums* out, bool accumulate, StreamId) override {
     cpu::heat_balance(t, p, out, accumulate);
   }
+  void steady_apply(const SteadyApplyParams& p, double* out, bool accumulate, StreamId) override {
+    cpu::steady_apply(DType::F64, p, out, accumulate);
+  }
+  void steady_update(const SteadyUpdateParams& p, double* out, bool accumulate, StreamId) override {
+    cpu::steady_update(DType::F64, p, out, accumulate);
+  }
+  void steady_direction(const SteadyDirectionParams& p, StreamId) override { cpu::steady_direction(DType::F64, p); }
+  void steady_scalars(SteadyState* st, int phase, StreamId) override { steady_scalars_step(st, phase); }
   void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
             StreamId) override {
     cpu::poke(t, f, L, i, j, k, value);

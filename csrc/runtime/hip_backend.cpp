@@ -159,6 +159,7 @@ class HipBackend final : public Backend {
       if (s) (void)hipStreamDestroy(s);
     if (err_scratch_) (void)hipFree(err_scratch_);
     if (bal_scratch_) (void)hipFree(bal_scratch_);
+    if (cg_scratch_) (void)hipFree(cg_scratch_);
     for (auto& s : streams_)
       if (s) (void)hipStreamDestroy(s);
   }
@@ -498,6 +499,20 @@ class HipBackend final : public Backend {
     if (!bal_scratch_) bal_scratch_ = alloc(hip::balance_scratch_bytes());
     op(s, [&](hipStream_t q) { hip::heat_balance(t, p, bal_scratch_, out, accumulate, q); });
   }
+  void steady_apply(const SteadyApplyParams& p, double* out, bool accumulate, StreamId s) override {
+    if (!cg_scratch_) cg_scratch_ = alloc(hip::steady_scratch_bytes());
+    op(s, [&](hipStream_t q) { hip::steady_apply(DType::F64, p, cg_scratch_, out, accumulate, q); });
+  }
+  void steady_update(const SteadyUpdateParams& p, double* out, bool accumulate, StreamId s) override {
+    if (!cg_scratch_) cg_scratch_ = alloc(hip::steady_scratch_bytes());
+    op(s, [&](hipStream_t q) { hip::steady_update(DType::F64, p, cg_scratch_, out, accumulate, q); });
+  }
+  void steady_direction(const SteadyDirectionParams& p, StreamId s) override {
+    op(s, [&](hipStream_t q) { hip::steady_direction(DType::F64, p, q); });
+  }
+  void steady_scalars(SteadyState* st, int phase, StreamId s) override {
+    op(s, [&](hipStream_t q) { hip::steady_scalars(st, phase, q); });
+  }
   void poke(DType t, void* f, const Layout& L, int64_t i, int64_t j, int64_t k, double value,
             StreamId s) override {
     op(s, [&](hipStream_t st) { hip::poke(t, f, L, i, j, k, value, st); });
@@ -603,6 +618,7 @@ class HipBackend final : public Backend {
   hipEvent_t fork_ev_ = nullptr, join_ev_[kNumStreams] = {nullptr, nullptr, nullptr};
   double* err_scratch_ = nullptr;
   void* bal_scratch_ = nullptr;  // heat_balance: per-block partials
+  void* cg_scratch_ = nullptr;   // steady solve: per-block partials of its dot products
   Roctx roctx_;
 };
 

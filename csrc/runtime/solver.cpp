@@ -479,6 +479,8 @@ Solver::~Solver() {
       if (f) be_->release(f);
     if (l.source) be_->release(l.source);
     if (l.cond) be_->release(l.cond);
+    if (l.steady_r) be_->release(l.steady_r);
+    if (l.steady_q) be_->release(l.steady_q);
     for (auto& io : l.faces) {
       be_->release(io.sendbuf);
       be_->release(io.recvbuf);
@@ -487,6 +489,8 @@ Solver::~Solver() {
   be_->release(dstate_);
   if (rstate_) be_->release(rstate_);
   if (bal_out_) be_->release(bal_out_);
+  if (cg_state_) be_->release(cg_state_);
+  if (cg_host_) be_->release_host(cg_host_);
   be_->release_host(hstate_);
   comm_.reset();  // communicators before the device
 }

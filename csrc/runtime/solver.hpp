@@ -65,6 +65,18 @@ struct HeatBalance {
   double imbalance = 0.0;     // sum of the flows + source_power = d(heat)/dt of the scheme
 };
 
+// Solver::solve_steady's report
+struct SteadyResult {
+  bool converged = false;      // the recomputed residual b - A x is within tol
+  int64_t iterations = 0;      // CG iterations whose update is in the field (exact)
+  double residual = 0.0;       // ||r|| / ||r0|| of the recurrence
+  double true_residual = 0.0;  // ||b - A x|| / ||r0||, recomputed on return
+  double r0_norm = 0.0;        // ||r0||, the 2-norm of the initial guess's residual
+  double seconds = 0.0;
+  int restarts = 0;            // restarts from the true residual (the recurrence met tol, b - A x did not)
+  int status = 0;              // SteadyStatus of the last recurrence
+};
+
 struct HostState {
   double norm, eps, last_residual, error_sum, error_count;
   int64_t iter, conv_iter;
@@ -195,6 +207,19 @@ class Solver {
   // --compat (UsageError).
   HeatBalance heat_balance();
 
+  // Direct steady-state solve (docs/ARCHITECTURE.md "Steady solve"): from the
+  // current field (the initial guess and the Dirichlet wall values, set_field)
+  // unpreconditioned conjugate gradients on the device on the symmetric positive
+  // definite system r(T) = G(T) - T = 0 of the current mode (conductivity,
+  // source, insulated / convective faces), until ||r_k|| <= tol ||r_0|| or
+  // max_iter iterations (<= 0: 10 (Nx + Ny + Nz)).  The solution becomes the
+  // current field and the time-step state restarts at iteration 0, as after
+  // set_field.  Dot products in double-double on a fixed reduction shape: the
+  // same solve returns the same bits; across decompositions results agree to
+  // the tolerance, not bitwise.  Synchronises; collective.  fp64 only, not with
+  // --compat, and not with every face insulated (UsageError).
+  SteadyResult solve_steady(double tol, int64_t max_iter = 0);
+
   // Field access.  gather_global fills `out` (N0*N1*N2 values as double,
   // z fastest) on the root process only; returns false elsewhere.
   bool gather_global(std::vector<double>* out);
@@ -301,6 +326,8 @@ class Solver {
     void* field[3] = {nullptr, nullptr, nullptr};  // nbuf_ of them in use
     void* source = nullptr;  // S = dtype(dt * q) in layout L, allocated by set_source
     void* cond = nullptr;    // Ch = dtype(0.5 * c) in layout L, allocated by set_conductivity
+    void* steady_r = nullptr;  // solve_steady: residual and A p, in layout L, allocated on first use
+    void* steady_q = nullptr;
     Box owned, interior;
     std::vector<Box> shell;
     std::vector<FaceIO> faces;
@@ -517,6 +544,10 @@ class Solver {
   DeviceState* dstate_ = nullptr;   // device
   DeviceState* rstate_ = nullptr;   // device scratch of resolve_coarse (allocated on first use)
   BalanceSums* bal_out_ = nullptr;  // device result of heat_balance (allocated on first use)
+  SteadyState* cg_state_ = nullptr; // solve_steady: device scalars and their pinned host mirror (first use)
+  SteadyState* cg_host_ = nullptr;
+  SteadyApplyParams steady_params(const Local& l) const;  // box, walls, D, Ch, S of a subdomain
+  void steady_allreduce(double* pair);
   DeviceState* hstate_ = nullptr;   // pinned host mirror
   int64_t issued_ = 0;              // iterations enqueued so far (absolute index)
   int cur_ = 0;               // buffer holding T^{issued_}

@@ -454,6 +454,28 @@ class HeatSolver:
         self._ensure()
         return dict(self._s.heat_balance())
 
+    def solve_steady(self, tol: float = 1e-8, max_iter: Optional[int] = None) -> Dict:
+        """Solve for the steady state directly: unpreconditioned conjugate
+        gradients on the device, from the current field (``set_field`` gives the
+        initial guess and the Dirichlet wall values), on the symmetric positive
+        definite system ``G(T) - T = 0`` of the current mode (conductivity,
+        source, insulated and convective faces), until the residual's 2-norm is
+        ``tol`` times the initial one or ``max_iter`` iterations (default
+        ``10 (Nx + Ny + Nz)``).  The solution becomes the current field and the
+        time-step state restarts at iteration 0, as after ``set_field``.
+
+        Returns ``converged`` (judged on the recomputed residual ``b - A x``),
+        ``iterations``, ``residual`` (relative, from the recurrence),
+        ``true_residual`` (relative, recomputed), ``r0_norm``, ``seconds``,
+        ``restarts`` (from the true residual, when the recurrence met ``tol``
+        and ``b - A x`` did not) and ``status``.  A repeated solve from the same
+        field returns the same bits; decompositions agree to the tolerance, not
+        bitwise.  fp64 only; not with ``compat``; a system with neither a
+        Dirichlet face nor a convective face with a positive coefficient is
+        singular: each a ``UsageError``.  Synchronises; collective."""
+        self._ensure()
+        return dict(self._s.solve_steady(float(tol), 0 if max_iter is None else int(max_iter)))
+
     def write_tecplot(self, path: str = "output/out.dat", layout: str = "auto") -> None:
         self._s.write_tecplot(path, layout)
 

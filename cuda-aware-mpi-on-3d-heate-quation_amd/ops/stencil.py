@@ -382,6 +382,99 @@ def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = Non
             "imbalance": total + source_power}
 
 
+def _steady_check(*fields: PaddedField) -> PaddedField:
+    f0 = fields[0]
+    for f in fields:
+        if f.dtype != torch.float64:
+            raise TypeError("the steady solve's operations take fp64 fields only")
+        if f.layout != f0.layout or f.device != f0.device:
+            raise ValueError("the fields must share one layout and device")
+    return f0
+
+
+def _steady_dot(f0: PaddedField, launch) -> Tuple[float, float]:
+    """Runs ``launch(dot_ptr, *gpu_args)`` and returns the (hi, lo) pair it wrote."""
+    ext = native()
+    dot = torch.zeros(2, dtype=torch.float64, device=f0.device)
+    if f0.device.type == "cuda":
+        scratch = torch.empty(ext.STEADY_SCRATCH_BYTES // 8, dtype=torch.int64, device=f0.device)
+        launch(dot.data_ptr(), scratch.data_ptr(), _stream_ptr(f0.flat))
+        dot = dot.cpu()
+    else:
+        launch(dot.data_ptr(), None, None)
+    return float(dot[0]), float(dot[1])
+
+
+def steady_apply(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Optional[Sequence[int]] = None,
+                 wall: Optional[Sequence[int]] = None, kind: Optional[Sequence[int]] = None,
+                 beta: Optional[Sequence[float]] = None, ambient: float = 0.0,
+                 source: Optional[PaddedField] = None, cond: Optional[PaddedField] = None,
+                 residual: bool = False) -> Tuple[float, float]:
+    """The steady solve's operator on ``box`` (default: all owned points), fp64:
+    ``dst = A src`` with the dot product ``src . dst``, or (``residual``)
+    ``dst = b - A src`` with ``dst . dst``, returned as the double-double pair
+    (hi, lo); the value is ``hi + lo``.
+
+    ``wall``: per face the local coordinate of the updated plane next to that
+    wall of the global grid, ``NO_WALL`` where it is out of reach (a subdomain's
+    inner sides); default: the owned block is the whole interior of its grid.
+    ``kind``: 0 Dirichlet (default), 1 insulated, 2 convective with ``beta``.
+    Across a wall the neighbour is: Dirichlet 0 (residual: the stored vertex),
+    insulated the centre, convective ``fma(beta, 0 - c, c)`` (residual: towards
+    ``ambient``).  ``cond``: Ch = 0.5 c; ``source``: S = dt q (residual only).
+    GPU tensors run steady_cg.hip on torch's current stream, CPU tensors the
+    definition; the field written is bitwise the same."""
+    ext = native()
+    f0 = _steady_check(src, dst)
+    n = f0.n
+    b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
+    w = list(wall) if wall is not None else [0, n[0] - 1, 0, n[1] - 1, 0, n[2] - 1]
+    kd = [int(v) for v in kind] if kind is not None else [0] * 6
+    bt = [float(v) for v in beta] if beta is not None else [0.0] * 6
+    args = (src.data_ptr(), dst.data_ptr(), list(n), [f0.gx, f0.gy, f0.gz], b, [float(v) for v in D],
+            _source_ptr(src, source), _cond_ptr(src, cond), w, kd, bt, float(ambient), bool(residual))
+
+    def launch(dot, scratch, stream):
+        if scratch is None:
+            ext.cpu.steady_apply(*args, dot)
+        else:
+            ext.hip.steady_apply(*args, scratch, dot, stream)
+
+    return _steady_dot(f0, launch)
+
+
+def steady_update(x: PaddedField, p: PaddedField, r: PaddedField, q: PaddedField, alpha: float,
+                  box: Optional[Sequence[int]] = None) -> Tuple[float, float]:
+    """``x += alpha p``, ``r -= alpha q`` on ``box`` (one fused multiply-add
+    each) and the new ``r . r`` as the double-double pair (hi, lo)."""
+    ext = native()
+    f0 = _steady_check(x, p, r, q)
+    n = f0.n
+    b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
+    args = (x.data_ptr(), p.data_ptr(), r.data_ptr(), q.data_ptr(), list(n), [f0.gx, f0.gy, f0.gz], b, float(alpha))
+
+    def launch(dot, scratch, stream):
+        if scratch is None:
+            ext.cpu.steady_update(*args, dot)
+        else:
+            ext.hip.steady_update(*args, scratch, dot, stream)
+
+    return _steady_dot(f0, launch)
+
+
+def steady_direction(p: PaddedField, r: PaddedField, beta: float, box: Optional[Sequence[int]] = None) -> None:
+    """``p = r + beta p`` on ``box``, one fused multiply-add per point."""
+    ext = native()
+    f0 = _steady_check(p, r)
+    n = f0.n
+    b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
+    args = (p.data_ptr(), r.data_ptr(), list(n), [f0.gx, f0.gy, f0.gz], b, float(beta))
+    if f0.device.type == "cuda":
+        ext.hip.steady_direction(*args, _stream_ptr(f0.flat))
+    else:
+        ext.cpu.steady_direction(*args)
+
+
 def init_field(f: PaddedField, gstart: Sequence[int], N: Sequence[int], h: Sequence[float]) -> None:
     """Analytic IC/BC into the padded field (reference heat3D.cu:408-453)."""
     ext = native()
