@@ -172,14 +172,26 @@ SteadyResult Solver::solve_steady(double tol, int64_t max_iter) {
   const auto t0 = std::chrono::steady_clock::now();
   SteadyResult res;
   double true_rr = 0.0;
+  bool finite = true;
   for (bool first = true;; first = false) {
     residual();
     pull_state();
     true_rr = hs.rrn[0] + hs.rrn[1];
     if (first) hs.rr0 = -1.0;  // (Init sets it from this residual)
     const double rr0 = first ? true_rr : hs.rr0;
-    const bool met = true_rr <= hs.tol2 * rr0;
-    if (met || !(true_rr == true_rr)) break;
+    // A finished call never reports kSteadyRunning: both exits below can be
+    // taken before the first kSteadyInit, while the status is still unset.
+    finite = true_rr == true_rr && true_rr <= 1.7976931348623157e308;
+    if (!finite) {
+      // a NaN or Inf in the field (or r . r overflows): nothing to iterate on
+      hs.status = kSteadyBreakdown;
+      break;
+    }
+    if (true_rr <= hs.tol2 * rr0) {
+      // (the first residual is its own reference: with tol < 1, met when it is zero)
+      if (first) hs.status = kSteadyConverged;
+      break;
+    }
     if (!first) {
       // the recurrence stopped: at the cap or broken down for good, or within
       // tol while the true residual is not: start again from the true residual
@@ -217,7 +229,7 @@ SteadyResult Solver::solve_steady(double tol, int64_t max_iter) {
   const double rec_rr = hs.rr0 >= 0.0 ? hs.rr : true_rr;
   res.residual = rr0 > 0.0 ? std::sqrt(rec_rr / rr0) : 0.0;
   res.true_residual = rr0 > 0.0 ? std::sqrt(true_rr / rr0) : 0.0;
-  res.converged = true_rr <= hs.tol2 * rr0;
+  res.converged = finite && true_rr <= hs.tol2 * rr0;
 
   // The solution becomes the state of iteration 0, as after set_field: the
   // insulated / convective wall planes show what they show after time steps,
