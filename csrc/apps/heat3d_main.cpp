@@ -97,6 +97,18 @@ static int drive(const Config& cfg, Solver& solver) {
       return 1;
     }
   }
+  // (and the heat capacity: values below 1 are found by the solver)
+  if (!cfg.capacity_file.empty()) {
+    try {
+      solver.set_capacity_file(cfg.capacity_file);
+    } catch (const UsageError& e) {
+      if (root) {
+        std::cout << Config::usage() << std::flush;
+        std::cerr << "heat3d: " << e.what() << std::endl;
+      }
+      return 1;
+    }
+  }
   solver.initialize();
   if (!cfg.initial_file.empty()) solver.set_field_file(cfg.initial_file);
   RunResult r;
@@ -181,6 +193,7 @@ static int drive(const Config& cfg, Solver& solver) {
     j.set_raw("dims", "[" + std::to_string(d.topo.dims[0]) + ", " + std::to_string(d.topo.dims[1]) +
                           ", " + std::to_string(d.topo.dims[2]) + "]");
     j.set("kernel", solver.kernel_name());
+    j.set_bool("has_capacity", solver.has_capacity());
     j.set_bool("conductivity_sweeps", cfg.cond_sweeps);
     j.set_bool("wall_source_sweeps", cfg.wall_source_sweeps);
     j.set("insulated", insulated_str(cfg.insulated));
@@ -225,6 +238,7 @@ static int drive(const Config& cfg, Solver& solver) {
     if (cfg.heat_balance) {
       io::Json b, fl;
       b.set("heat", hb.heat);
+      b.set_bool("capacity", hb.capacity);
       b.set("t_min", hb.t_min);
       b.set("t_max", hb.t_max);
       b.set("nonfinite", (int64_t)hb.nonfinite);

@@ -197,6 +197,9 @@ std::string Config::usage() {
      << "                            float64, NX*NY*NZ values, z fastest (the checkpoint field file's order)\n"
      << "  --conductivity FILE       relative conductivity c, 0 < c <= 1 (T_t = div(alpha c grad T) + q), same format\n"
      << "                            as --source; iterations then run as single steps (no K-step sweeps)\n"
+     << "  --capacity FILE           relative volumetric heat capacity rc >= 1 (rc T_t = div(alpha c grad T) + q), same\n"
+     << "                            format as --source; iterations then run as single steps (no K-step sweeps;\n"
+     << "                            not with --compat)\n"
      << "  --insulated FACES         zero-flux (adiabatic) walls: a list of x-,x+,y-,y+,z-,z+ or all; the other\n"
      << "                            faces stay Dirichlet (not with --compat)\n"
      << "  --convective FACE=BETA,.. convective (Robin) walls, -k dT/dn = h (T - T_inf): a list such as y-=0.5,x+=0.25\n"
@@ -362,6 +365,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--source") c.source_file = get("--source");
     else if (key == "--initial") c.initial_file = get("--initial");
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
+    else if (key == "--capacity") c.capacity_file = get("--capacity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
     else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
     else if (key == "--heat-balance") c.heat_balance = true;
@@ -474,10 +478,13 @@ Config Config::parse(int argc, const char* const* argv) {
   if (c.watchdog_s <= 0) throw UsageError("--watchdog must be > 0");
   if (c.progress_s < 0) throw UsageError("--progress must be >= 0");
   if (c.time_limit_s < 0) throw UsageError("--time-limit must be >= 0");
-  // --source / --initial / --conductivity: NX*NY*NZ float64 values; a wrong size is a usage error
-  for (const auto* f : {&c.source_file, &c.initial_file, &c.conductivity_file}) {
+  // --source / --initial / --conductivity / --capacity: NX*NY*NZ float64 values; a wrong size is a usage error
+  for (const auto* f : {&c.source_file, &c.initial_file, &c.conductivity_file, &c.capacity_file}) {
     if (f->empty()) continue;
-    const char* flag = f == &c.source_file ? "--source" : f == &c.initial_file ? "--initial" : "--conductivity";
+    const char* flag = f == &c.source_file         ? "--source"
+                       : f == &c.initial_file      ? "--initial"
+                       : f == &c.conductivity_file ? "--conductivity"
+                                                   : "--capacity";
     struct stat st {};
     if (::stat(f->c_str(), &st) != 0) throw UsageError(std::string(flag) + ": cannot read file " + *f);
     const long long want = (long long)c.n[0] * c.n[1] * c.n[2] * 8;
@@ -490,6 +497,8 @@ Config Config::parse(int argc, const char* const* argv) {
     throw UsageError("--source / --initial / --conductivity are not part of --scheme reference");
   if (!c.conductivity_file.empty() && c.compat)
     throw UsageError("--conductivity is not part of --compat (the reference's uniform material)");
+  if (!c.capacity_file.empty() && (c.compat || c.scheme == "reference"))
+    throw UsageError("--capacity is not part of --compat / --scheme reference (the reference's uniform material)");
   if (c.insulated && (c.compat || c.scheme == "reference"))
     throw UsageError("--insulated is not part of --compat / --scheme reference (the reference's Dirichlet walls)");
   if (convective_mask(c.convective) && (c.compat || c.scheme == "reference"))

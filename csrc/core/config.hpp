@@ -83,6 +83,7 @@ struct Config {
   // ITER_MAX caps the CG iterations; a "steady_solve" object in --json-out.
   bool steady_solve = false;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
+  std::string capacity_file;  // --capacity: relative volumetric heat capacity rc >= 1, same format
   std::string initial_file;  // --initial: initial field with its wall values, same format
   // --insulated: faces of the global grid that are zero-flux walls instead of
   // Dirichlet ones, bit 2 * axis + side (x-, x+, y-, y+, z-, z+; parse_insulated)

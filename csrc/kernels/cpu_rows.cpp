@@ -120,13 +120,71 @@ static double row_var(const RowArgs<Real>& a) {
   return row_var_loop<Real, SRC, WALL>(a.in, a.out, a.cond, a.src, a);
 }
 
+// The update with a heat capacity (StencilParams::cap) in the form (COND, SRC,
+// WALL): the same ghost substitution, then the increment of the step started
+// from zero (steady_increment / steady_increment_var), the source added to it,
+// and cap_update: T' = fma(s, u, T) with s read at the updated point only.
+template <typename Real, bool COND, bool SRC, WallKind WALL>
+static inline double row_cap_loop(const Real* __restrict in, Real* __restrict out,
+                                  [[maybe_unused]] const Real* __restrict h,
+                                  [[maybe_unused]] const Real* __restrict src, const Real* __restrict cap,
+                                  const RowArgs<Real>& a) {
+  const int64_t n = a.n;
+  const Real Dx = a.Dx, Dy = a.Dy, Dz = a.Dz;
+  const int64_t sx = a.sx, sy = a.sy;
+  [[maybe_unused]] const int64_t oxm = a.oxm, oxp = a.oxp, oym = a.oym, oyp = a.oyp, kzm = a.kzm, kzp = a.kzp;
+  [[maybe_unused]] Real bxm = 0, bxp = 0, bym = 0, byp = 0, bzm = 0, bzp = 0, tinf = 0;
+  if constexpr (WALL == WallKind::Convective) {
+    bxm = a.beta[0], bxp = a.beta[1], bym = a.beta[2], byp = a.beta[3], bzm = a.beta[4], bzp = a.beta[5];
+    tinf = a.tinf;
+  }
+  double lres = 0.0;
+  bool nan = false;
+  for (int64_t k = 0; k < n; ++k) {
+    const Real T = in[k];
+    Real xm, xp, ym, yp, zm, zp;
+    if constexpr (WALL == WallKind::None) {
+      xm = in[k - sx], xp = in[k + sx], ym = in[k - sy], yp = in[k + sy], zm = in[k - 1], zp = in[k + 1];
+    } else if constexpr (WALL == WallKind::Insulated) {
+      xm = in[k + oxm], xp = in[k + oxp], ym = in[k + oym], yp = in[k + oyp];
+      zm = k == kzm ? T : in[k - 1], zp = k == kzp ? T : in[k + 1];
+    } else {
+      const Real d = tinf - T;
+      xm = oxm ? in[k + oxm] : h3d_fma(bxm, d, T), xp = oxp ? in[k + oxp] : h3d_fma(bxp, d, T);
+      ym = oym ? in[k + oym] : h3d_fma(bym, d, T), yp = oyp ? in[k + oyp] : h3d_fma(byp, d, T);
+      zm = k == kzm ? h3d_fma(bzm, d, T) : in[k - 1], zp = k == kzp ? h3d_fma(bzp, d, T) : in[k + 1];
+    }
+    Real u;
+    if constexpr (COND)
+      u = steady_increment_var<Real>(T, xm, xp, ym, yp, zm, zp, h[k], h[k - sx], h[k + sx], h[k - sy], h[k + sy],
+                                     h[k - 1], h[k + 1], Dx, Dy, Dz);
+    else u = steady_increment<Real>(T, xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);
+    if constexpr (SRC) u = add_source<Real>(u, src[k]);
+    const Real nv = cap_update<Real>(cap[k], u, T);
+    out[k] = nv;
+    const double d = resid_abs(nv, T);
+    nan |= d != d;
+    lres = d > lres ? d : lres;
+  }
+  return nan ? std::nan("") : lres;
+}
+
+template <typename Real, bool COND, bool SRC, WallKind WALL>
+static double row_cap(const RowArgs<Real>& a) {
+  return row_cap_loop<Real, COND, SRC, WALL>(a.in, a.out, a.cond, a.src, a.cap, a);
+}
+
 template <typename Real>
 static constexpr RowTable<Real> make_table() {
   constexpr WallKind N = WallKind::None, I = WallKind::Insulated, C = WallKind::Convective;
   return {{{row<Real, false, N>, row<Real, false, I>, row<Real, false, C>},
            {row<Real, true, N>, row<Real, true, I>, row<Real, true, C>}},
           {{row_var<Real, false, N>, row_var<Real, false, I>, row_var<Real, false, C>},
-           {row_var<Real, true, N>, row_var<Real, true, I>, row_var<Real, true, C>}}};
+           {row_var<Real, true, N>, row_var<Real, true, I>, row_var<Real, true, C>}},
+          {{{row_cap<Real, false, false, N>, row_cap<Real, false, false, I>, row_cap<Real, false, false, C>},
+            {row_cap<Real, false, true, N>, row_cap<Real, false, true, I>, row_cap<Real, false, true, C>}},
+           {{row_cap<Real, true, false, N>, row_cap<Real, true, false, I>, row_cap<Real, true, false, C>},
+            {row_cap<Real, true, true, N>, row_cap<Real, true, true, I>, row_cap<Real, true, true, C>}}}};
 }
 
 // (constant-initialised: nothing of this build runs before it is chosen)

@@ -10,7 +10,8 @@
 //
 // One row template covers the forms of the uniform update (kernels.hpp
 // SweepForm: with or without a heat source, behind no, insulated or convective
-// walls), a second one the same forms of the update with a conductivity field.
+// walls), a second one the same forms of the update with a conductivity field,
+// a third one the forms with a heat capacity (with or without a conductivity).
 // Every row has the same signature, and each build exports one table of them.
 #pragma once
 
@@ -31,6 +32,7 @@ struct RowArgs {
   Real Dx, Dy, Dz;
   const Real* src;   // heat source: src[k] is added to the finished update (ftcs_update_src)
   const Real* cond;  // conductivity form (ftcs_update_var; with src != nullptr ftcs_update_var_src)
+  const Real* cap;   // heat-capacity forms only: s = dtype(1 / rc), cap[k] scales the increment (cap_update)
   int64_t sx, sy;    // strides of the x and y neighbours (the forms without walls)
   // walls (StencilParams::wall): the offsets of the x and y neighbours, 0 where
   // the neighbour's temperature across a wall is replaced by the ghost value
@@ -53,8 +55,12 @@ template <typename Real>
 struct RowTable {
   RowFn<Real> row[2][3];  // [SweepForm::src][SweepForm::wall]
   RowFn<Real> var[2][3];  // the conductivity forms, by the same indices
+  // the heat-capacity forms (StencilParams::cap): [conductivity][src][wall]
+  RowFn<Real> cap[2][2][3];
   // the row of a call: its form, and whether it has a conductivity
   RowFn<Real> of(SweepForm f, bool cond) const { return (cond ? var : row)[f.src][(int)f.wall]; }
+  // ... of a call with a heat capacity
+  RowFn<Real> of_cap(SweepForm f, bool cond) const { return cap[cond][f.src][(int)f.wall]; }
 };
 
 struct RowKernels {

@@ -5,7 +5,8 @@
 // the grid, ...) and reads them in 16-byte pieces per lane from the aligned
 // start below the box (the elements outside [lo, hi) are masked, and lie inside
 // the row's pitch); four pieces are loaded ahead of the arithmetic.  The source
-// and the conductivity are template arguments: the plain form reads one field.
+// the conductivity and the heat capacity are template arguments: the plain form
+// reads one field.
 // Face terms are formed on wall-adjacent rows only: the x and y faces under
 // wave-uniform branches (the neighbour row is one more vector load), the two
 // z faces of a row by lanes 0 and 1 after the row.  Every lane keeps eight
@@ -132,7 +133,7 @@ __device__ __forceinline__ void face_point(LaneSums<Real>& s, const BalanceParam
   dd_add(s.acc[2 + F], term);
 }
 
-template <typename Real, int V, bool SRC, bool COND>
+template <typename Real, int V, bool SRC, bool COND, bool CAP>
 __global__ __launch_bounds__(kBalThreads) void balance_partial_kernel(BalanceParams p, BalanceSums* partial) {
   typedef typename VecOf<Real, V>::type Vec;
   typedef typename KeyOf<Real>::type Key;
@@ -141,6 +142,7 @@ __global__ __launch_bounds__(kBalThreads) void balance_partial_kernel(BalancePar
   const Real* T = static_cast<const Real*>(p.field);
   const Real* S = static_cast<const Real*>(p.src);
   const Real* Ch = static_cast<const Real*>(p.cond);
+  [[maybe_unused]] const Real* Cs = static_cast<const Real*>(p.cap);
   const Layout& L = p.L;
   const Box& b = p.box;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -165,12 +167,14 @@ __global__ __launch_bounds__(kBalThreads) void balance_partial_kernel(BalancePar
     const bool faces = xm | xp | ym | yp;
     for (int64_t k0 = kb + (int64_t)lane * V; k0 < hi; k0 += (int64_t)64 * V * kBalAhead) {
       Vec t[kBalAhead], q[kBalAhead];
+      [[maybe_unused]] Vec sc[kBalAhead];
 #pragma unroll
       for (int u = 0; u < kBalAhead; ++u) {
         const int64_t k = k0 + (int64_t)u * 64 * V;
         if (k < hi) {
           t[u] = *reinterpret_cast<const Vec*>(T + base + k);
           if constexpr (SRC) q[u] = *reinterpret_cast<const Vec*>(S + base + k);
+          if constexpr (CAP) sc[u] = *reinterpret_cast<const Vec*>(Cs + base + k);
         }
       }
 #pragma unroll
@@ -190,7 +194,15 @@ __global__ __launch_bounds__(kBalThreads) void balance_partial_kernel(BalancePar
             else qv = q[u][v];
           }
           c[v] = ok[v] ? tv : Real(0);
-          dd_add(s.acc[0], static_cast<double>(c[v]));
+          if constexpr (CAP) {
+            // stored heat rc T = T / s, the quotient in double (s = 1 outside the box)
+            Real sv;
+            if constexpr (V == 1) sv = sc[u];
+            else sv = sc[u][v];
+            dd_add(s.acc[0], static_cast<double>(c[v]) / static_cast<double>(ok[v] ? sv : Real(1)));
+          } else {
+            dd_add(s.acc[0], static_cast<double>(c[v]));
+          }
           s.bad += bal_nonfinite(c[v]) ? 1u : 0u;
           const Key key = bal_key(c[v]);
           const bool num = ok[v] && c[v] == c[v];
@@ -241,13 +253,19 @@ __global__ __launch_bounds__(kBalThreads) void balance_final_kernel(const Balanc
   }
 }
 
+template <typename Real, int V, bool CAP>
+static void launch_partial_cap(const BalanceParams& p, int blocks, BalanceSums* partial, hipStream_t q) {
+  const dim3 g((unsigned)blocks), b(kBalThreads);
+  if (p.src && p.cond) hipLaunchKernelGGL((balance_partial_kernel<Real, V, true, true, CAP>), g, b, 0, q, p, partial);
+  else if (p.src) hipLaunchKernelGGL((balance_partial_kernel<Real, V, true, false, CAP>), g, b, 0, q, p, partial);
+  else if (p.cond) hipLaunchKernelGGL((balance_partial_kernel<Real, V, false, true, CAP>), g, b, 0, q, p, partial);
+  else hipLaunchKernelGGL((balance_partial_kernel<Real, V, false, false, CAP>), g, b, 0, q, p, partial);
+}
+
 template <typename Real, int V>
 static void launch_partial(const BalanceParams& p, int blocks, BalanceSums* partial, hipStream_t q) {
-  const dim3 g((unsigned)blocks), b(kBalThreads);
-  if (p.src && p.cond) hipLaunchKernelGGL((balance_partial_kernel<Real, V, true, true>), g, b, 0, q, p, partial);
-  else if (p.src) hipLaunchKernelGGL((balance_partial_kernel<Real, V, true, false>), g, b, 0, q, p, partial);
-  else if (p.cond) hipLaunchKernelGGL((balance_partial_kernel<Real, V, false, true>), g, b, 0, q, p, partial);
-  else hipLaunchKernelGGL((balance_partial_kernel<Real, V, false, false>), g, b, 0, q, p, partial);
+  if (p.cap) launch_partial_cap<Real, V, true>(p, blocks, partial, q);
+  else launch_partial_cap<Real, V, false>(p, blocks, partial, q);
 }
 
 void heat_balance(DType t, const BalanceParams& p, void* scratch, BalanceSums* out, bool accumulate, void* stream) {
@@ -261,7 +279,7 @@ void heat_balance(DType t, const BalanceParams& p, void* scratch, BalanceSums* o
   BalanceSums* partial = static_cast<BalanceSums*>(scratch);
   // 16-byte pieces need 16-byte aligned fields (rows start at multiples of 16 elements)
   const auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; };
-  const bool wide = al(p.field) && al(p.src) && al(p.cond);
+  const bool wide = al(p.field) && al(p.src) && al(p.cond) && al(p.cap);
   if (t == DType::F64) {
     if (wide) launch_partial<double, 2>(p, blocks, partial, S(stream));
     else launch_partial<double, 1>(p, blocks, partial, S(stream));

@@ -3,7 +3,8 @@
 // kernel (heat_balance.hip) share.
 //
 // Over the updated points U of a box (docs/ARCHITECTURE.md "Heat balance"):
-//   sum 0      Σ T                      (stored heat / (hx hy hz))
+//   sum 0      Σ T                      (stored heat / (hx hy hz); with a heat
+//              capacity Σ T / s, s = dtype(1 / rc), each term double(T) / double(s))
 //   sum 1      Σ S                      (source power * dt / (hx hy hz))
 //   sum 2 + f  Σ w (n - c) over the points whose neighbour across face f is a
 //              wall vertex (flow / (alpha h_b h_c / h_a))
@@ -30,6 +31,7 @@ struct BalanceParams {
   const void* field = nullptr;  // T
   const void* src = nullptr;    // S = dtype(dt q) in the same Layout, or nullptr
   const void* cond = nullptr;   // Ch = dtype(0.5 c) in the same Layout, or nullptr
+  const void* cap = nullptr;    // s = dtype(1 / rc) in the same Layout, or nullptr
   Layout L;
   Box box;  // local coordinates of the updated points to sum (inside the owned block)
   // local coordinate along axis a of the updated plane next to the low / high

@@ -131,6 +131,17 @@ struct StencilParams {
   // stencil_tbl_conv_src.hip) and of the tv sweep (stencil_tbv_conv.hip).
   double wall_beta[3][2] = {{-1, -1}, {-1, -1}, {-1, -1}};
   double ambient = 0;
+  // Relative volumetric heat capacity rc >= 1, stored as s = dtype(1 / rc) in
+  // (0, 1]: a static field in the same Layout, of which only the centre value
+  // of an updated point is read (ghosts and wall vertices hold 1).  Every
+  // updated point is evaluated by cap_update below: the increment of the step
+  // (steady_increment / steady_increment_var, plus the source) scaled by s in
+  // one fused multiply-add onto the centre value.  nullptr: one capacity
+  // everywhere, the kernels above.  Honoured by cpu::stencil / stencil_multi
+  // (with `wall` / `wall_beta` too) and by the single-step gfx950 kernels of
+  // stencil_cap.hip (hip::stencil dispatches there); every other gfx950
+  // stencil entry refuses it with an Error.  Not part of form().
+  const void* cap = nullptr;
   // the one place that reads src, wall and wall_beta for the form of the call
   SweepForm form() const {
     SweepForm f;
@@ -170,6 +181,8 @@ void init_field(DType t, const InitParams& p, void* stream);
 void stencil(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 // its conductivity forms (stencil_var.hip; stencil() dispatches here when p.cond is set)
 void stencil_var(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
+// its heat-capacity forms (stencil_cap.hip; stencil() dispatches here when p.cap is set)
+void stencil_cap(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 // K-step temporally blocked sweep, lean kernel (stencil_tbl.hip), K = k.K
 void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 // z tile stride of the lean kernel for a box (host-side choice, stencil_tbl.hip)
@@ -475,6 +488,16 @@ H3D_HD inline Real steady_increment_var(Real c, Real xm, Real xp, Real ym, Real 
   const Real fy = var_flux<Real>(c, ym, yp, hc + hym, hc + hyp);
   const Real fz = var_flux<Real>(c, zm, zp, hc + hzm, hc + hzp);
   return h3d_fma(Dz, fz, h3d_fma(Dy, fy, Dx * fx));
+}
+// One step with a heat capacity, rc T_t = div(alpha c grad T) + q: the
+// increment u of the step (steady_increment or steady_increment_var, then
+// add_source) scaled by s = dtype(1 / rc) and added to the centre value in one
+// fused multiply-add.  s <= 1, so T' stays a convex combination of T's seven
+// points under the time step of the uniform problem.  With s == 1 it equals
+// ftcs_update (whose chain starts from c) up to rounding, not bitwise.
+template <typename Real>
+H3D_HD inline Real cap_update(Real s, Real u, Real c) {
+  return h3d_fma(s, u, c);
 }
 // The neighbour of c across a wall of the global grid (cpu_rows.cpp's ghost
 // rules): an insulated face shows the centre value, a convective one its ghost

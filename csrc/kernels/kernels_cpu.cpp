@@ -72,13 +72,15 @@ static void stencil_t(const StencilParams& p) {
   unsigned long long resbits = 0;
   // the row of the call's form (cpu_rows.hpp): one lookup, one call per row
   const SweepForm form = p.form();
-  const RowFn<Real> rowfn = cpu_row_kernels().of<Real>().of(form, p.cond != nullptr);
+  const RowTable<Real>& rows = cpu_row_kernels().of<Real>();
+  const RowFn<Real> rowfn = p.cap ? rows.of_cap(form, p.cond != nullptr) : rows.of(form, p.cond != nullptr);
   // convective walls (StencilParams::wall_beta): the coefficients in the
   // field's dtype, 0 on the insulated faces of the same call
   Real beta[6];
   for (int f = 0; f < 6; ++f) beta[f] = static_cast<Real>(p.wall_beta[f / 2][f % 2] > 0 ? p.wall_beta[f / 2][f % 2] : 0);
   const Real* src = static_cast<const Real*>(p.src);    // heat source S, or nullptr
   const Real* cond = static_cast<const Real*>(p.cond);  // conductivity Ch, or nullptr
+  const Real* cap = static_cast<const Real*>(p.cap);    // heat capacity s = 1 / rc, or nullptr
   RowArgs<Real> row{};
   row.n = b.extent(2);
   row.Dx = Dx, row.Dy = Dy, row.Dz = Dz;
@@ -95,6 +97,7 @@ static void stencil_t(const StencilParams& p) {
       a.out = out + c;
       a.src = src ? src + c : nullptr;
       a.cond = cond ? cond + c : nullptr;
+      a.cap = cap ? cap + c : nullptr;
       // insulated / convective walls (StencilParams::wall): offset 0 where the neighbour is the ghost
       a.oxm = i == p.wall[0][0] ? 0 : -sx, a.oxp = i == p.wall[0][1] ? 0 : sx;
       a.oym = j == p.wall[1][0] ? 0 : -sy, a.oyp = j == p.wall[1][1] ? 0 : sy;
@@ -283,6 +286,7 @@ static void balance_chunk(const BalanceParams& p, int64_t r0, int64_t r1, Balanc
   const Real* T = static_cast<const Real*>(p.field);
   const Real* S = static_cast<const Real*>(p.src);
   const Real* Ch = static_cast<const Real*>(p.cond);
+  const Real* Cs = static_cast<const Real*>(p.cap);
   const Layout& L = p.L;
   const Box& b = p.box;
   const int64_t ey = b.extent(1);
@@ -311,7 +315,8 @@ static void balance_chunk(const BalanceParams& p, int64_t r0, int64_t r1, Balanc
     for (int64_t k = b.lo[2]; k < b.hi[2]; ++k) {
       const int64_t idx = L.index(i, j, k);
       const Real c = T[idx];
-      dd_add(acc[0], static_cast<double>(c));
+      // stored heat: T, or with a heat capacity rc T = T / s, the quotient in double
+      dd_add(acc[0], Cs ? static_cast<double>(c) / static_cast<double>(Cs[idx]) : static_cast<double>(c));
       bad += bal_nonfinite(c);
       if (c == c) {
         const long long key = bal_key(static_cast<double>(c));

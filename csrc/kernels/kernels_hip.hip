@@ -596,6 +596,7 @@ void stencil(DType t, const StencilParams& p, const KernelSpec& k, void* stream)
   // (never Dirichlet arithmetic next to an insulated wall)
   HEAT3D_CHECK(!p.has_walls(), "the single-step kernels take no StencilParams::wall: copy the wall planes from their "
                                "inward neighbours before the step (Solver::refresh_walls)");
+  if (p.cap) return stencil_cap(t, p, k, stream);   // heat-capacity forms (stencil_cap.hip), with or without p.cond
   if (p.cond) return stencil_var(t, p, k, stream);  // conductivity forms (stencil_var.hip)
   if (k.kind == KernelSpec::Naive) {
     if (t == DType::F64) launch_naive<double>(p, S(stream));

@@ -136,6 +136,10 @@ void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
 
 // (every K-step launch comes through stencil_lean or stencil_lean_pair)
 void refuse_conductivity(const StencilParams& p, const KernelSpec& k) {
+  // (never the arithmetic of one capacity where the call has a capacity field)
+  if (p.cap)
+    HEAT3D_THROW("K-step sweep kernel " << k.str() << " has no heat-capacity form: with a capacity field every "
+                                                     "iteration runs as a single step (tile | naive)");
   // nor do the pair kernel (spec field V = 2, asked for by name: with walls an
   // unset V means 1 for either dtype) and the tv kernels have a wall form;
   // stencil_lean goes on to the lean kernel's wall forms after this check

@@ -108,6 +108,9 @@ static const char* tbv_form_name(SweepForm f) {
 void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   HEAT3D_CHECK(k.kind == KernelSpec::TBV, "stencil_cond_sweep needs a tv kernel");
   if (!p.cond) HEAT3D_THROW("tv kernels need a conductivity field (" << k.str() << " without one; use tl2..tl6)");
+  if (p.cap)
+    HEAT3D_THROW("tv kernel " << k.str() << " has no heat-capacity form: with a capacity field every iteration runs "
+                                            "as a single step (tile | naive)");
   HEAT3D_CHECK(!p.fuse_check && !p.tune, "tv kernels have no fused check and no schedule tuning");
   if (p.box.empty()) return;
   const SweepForm form = p.form();

@@ -327,6 +327,7 @@ static void dispatch_var(const StencilParams& p, const KernelSpec& k, hipStream_
 void stencil_var(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
   if (p.box.empty()) return;
   HEAT3D_CHECK(p.cond, "stencil_var needs a conductivity field");
+  HEAT3D_CHECK(!p.cap, "stencil_var has no heat-capacity form (stencil_cap.hip has; hip::stencil dispatches there)");
   HEAT3D_CHECK(k.kind == KernelSpec::Naive || k.kind == KernelSpec::Tile, "single-step kernels: naive | tile");
   if (t == DType::F64) {
     if (p.src) dispatch_var<double, true>(p, k, S(stream));

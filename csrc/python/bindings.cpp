@@ -149,11 +149,12 @@ void set_conv(StencilParams& p, const std::array<double, 6>& c, double ambient) 
 BalanceParams bparams(int64_t field_ptr, const std::array<int64_t, 3>& n, int64_t esize, const std::array<int64_t, 3>& g,
                       const std::array<int64_t, 6>& box, int64_t src_ptr, int64_t cond_ptr,
                       const std::array<int64_t, 6>& wall, const std::array<int, 6>& kind,
-                      const std::array<double, 6>& beta, double ambient) {
+                      const std::array<double, 6>& beta, double ambient, int64_t cap_ptr = 0) {
   BalanceParams p;
   p.field = reinterpret_cast<const void*>(field_ptr);
   p.src = reinterpret_cast<const void*>(src_ptr);
   p.cond = reinterpret_cast<const void*>(cond_ptr);
+  p.cap = reinterpret_cast<const void*>(cap_ptr);
   p.L = to_layout(n, esize, g[0], g[1], g[2]);
   p.box = to_box(box);
   for (int a = 0; a < 3; ++a) {
@@ -622,14 +623,18 @@ PYBIND11_MODULE(_heat3d, m) {
   py::module_ hk = m.def_submodule("hip", "gfx950 kernels on device pointers");
   hk.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
-                       const std::string& kernel, int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
+                       const std::string& kernel, int64_t stream, int64_t src_ptr, int64_t cond_ptr,
+                       int64_t cap_ptr, std::array<int64_t, 3> g) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
+    p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     hip::stencil(t, p, KernelSpec::parse(kernel), reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
-     py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0,
+     py::arg("cap_ptr") = 0, py::arg("g") = std::array<int64_t, 3>{1, 1, 1});
   hk.def("stencil2", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                         std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                         int64_t stream) {
@@ -648,7 +653,7 @@ PYBIND11_MODULE(_heat3d, m) {
   hk.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                             int64_t stream, int64_t src_ptr, int64_t cond_ptr) {
+                             int64_t stream, int64_t src_ptr, int64_t cond_ptr, int64_t cap_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), gx);
@@ -656,19 +661,21 @@ PYBIND11_MODULE(_heat3d, m) {
     p.ux[1] = ux[1];
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("gx"), py::arg("box"),
      py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
-     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("cap_ptr") = 0);
   // deep ghosts on every axis (block decompositions): g = (gx, gy, gz),
   // u = update ranges (ux0, ux1, uy0, uy1, uz0, uz1)
   hk.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                               int64_t stream, int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient,
+                              int64_t cap_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -681,13 +688,14 @@ PYBIND11_MODULE(_heat3d, m) {
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
     set_conv(p, conv, ambient);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     hip::sweep(t, p, k, reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("stream"),
      py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
-     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0, py::arg("cap_ptr") = 0);
   hk.def("init_field", [](const std::string& dt, int64_t ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> gstart,
                           std::array<int64_t, 3> N, std::array<double, 3> h, int64_t stream) {
     DType t = dt_of(dt);
@@ -722,14 +730,14 @@ PYBIND11_MODULE(_heat3d, m) {
   hk.def("heat_balance", [](const std::string& dt, int64_t field_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
                             std::array<int64_t, 6> box, int64_t src_ptr, int64_t cond_ptr, std::array<int64_t, 6> wall,
                             std::array<int, 6> kind, std::array<double, 6> beta, double ambient, int64_t scratch_ptr,
-                            int64_t out_ptr, bool accumulate, int64_t stream) {
+                            int64_t out_ptr, bool accumulate, int64_t stream, int64_t cap_ptr) {
     DType t = dt_of(dt);
-    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient);
+    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient, cap_ptr);
     hip::heat_balance(t, p, reinterpret_cast<void*>(scratch_ptr), reinterpret_cast<BalanceSums*>(out_ptr), accumulate,
                       reinterpret_cast<void*>(stream));
   }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
      py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("scratch_ptr"),
-     py::arg("out_ptr"), py::arg("accumulate"), py::arg("stream"));
+     py::arg("out_ptr"), py::arg("accumulate"), py::arg("stream"), py::arg("cap_ptr") = 0);
   // the steady solve's operations (kernels/steady_cg.hpp), fp64: out_ptr = 2 doubles (hi, lo) of device
   // memory, scratch_ptr = STEADY_SCRATCH_BYTES of device memory
   hk.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
@@ -758,18 +766,22 @@ PYBIND11_MODULE(_heat3d, m) {
   ck.def("stencil", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                        std::array<int64_t, 6> box, std::array<double, 3> D, int64_t state_ptr, int slot,
                        int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient,
+                              int64_t cap_ptr, std::array<int64_t, 3> g) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
+    p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
     set_conv(p, conv, ambient);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     py::gil_scoped_release nogil;
     cpu::stencil(t, p);
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("box"), py::arg("D"),
      py::arg("state_ptr"), py::arg("slot"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
-     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0, py::arg("cap_ptr") = 0,
+     py::arg("g") = std::array<int64_t, 3>{1, 1, 1});
   // one row of the convective-wall update in either build of the row kernels
   // (cpu_rows.hpp; "fma" needs a CPU with FMA + AVX2: see cpu.has_fma): off =
   // element offsets of the x-, x+, y-, y+ neighbours (0: across a wall), kz =
@@ -804,7 +816,7 @@ PYBIND11_MODULE(_heat3d, m) {
   ck.def("stencil_sweep", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                              int64_t gx, std::array<int64_t, 6> box, std::array<int64_t, 2> ux,
                              std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
-                             int64_t src_ptr, int64_t cond_ptr) {
+                             int64_t src_ptr, int64_t cond_ptr, int64_t cap_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), gx);
@@ -812,18 +824,21 @@ PYBIND11_MODULE(_heat3d, m) {
     p.ux[1] = ux[1];
     p.src = reinterpret_cast<const void*>(src_ptr);
     p.cond = reinterpret_cast<const void*>(cond_ptr);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
     py::gil_scoped_release nogil;
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("gx"), py::arg("box"),
-     py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0);
+     py::arg("ux"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0,
+     py::arg("cap_ptr") = 0);
   ck.def("stencil_sweep3", [](const std::string& dt, int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n,
                               std::array<int64_t, 3> g, std::array<int64_t, 6> box, std::array<int64_t, 6> u,
                               std::array<double, 3> D, int64_t state_ptr, int slot, const std::string& kernel,
                               int64_t src_ptr, int64_t cond_ptr,
-                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient) {
+                              std::array<int64_t, 6> walls, std::array<double, 6> conv, double ambient,
+                              int64_t cap_ptr) {
     DType t = dt_of(dt);
     auto p = sparams(in_ptr, out_ptr, n, (int64_t)dtype_size(t), box, D, state_ptr, slot);
     p.L = to_layout(n, (int64_t)dtype_size(t), g[0], g[1], g[2]);
@@ -836,6 +851,7 @@ PYBIND11_MODULE(_heat3d, m) {
     p.cond = reinterpret_cast<const void*>(cond_ptr);
     set_walls(p, walls);
     set_conv(p, conv, ambient);
+    p.cap = reinterpret_cast<const void*>(cap_ptr);
     KernelSpec k = KernelSpec::parse(kernel);
     if (!k.multi_step()) throw UsageError("stencil_sweep3 needs a tl2..tl6 kernel");
     std::vector<char> s0(p.L.bytes()), s1(p.L.bytes());
@@ -843,18 +859,18 @@ PYBIND11_MODULE(_heat3d, m) {
     cpu::stencil_multi(t, p, k.K, s0.data(), s1.data());
   }, py::arg("dtype"), py::arg("in_ptr"), py::arg("out_ptr"), py::arg("n"), py::arg("g"), py::arg("box"),
      py::arg("u"), py::arg("D"), py::arg("state_ptr"), py::arg("slot"), py::arg("kernel"), py::arg("src_ptr") = 0, py::arg("cond_ptr") = 0, py::arg("walls") = kNoWalls,
-     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0);
+     py::arg("conv") = kNoConv, py::arg("ambient") = 0.0, py::arg("cap_ptr") = 0);
   ck.def("heat_balance", [](const std::string& dt, int64_t field_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
                             std::array<int64_t, 6> box, int64_t src_ptr, int64_t cond_ptr, std::array<int64_t, 6> wall,
                             std::array<int, 6> kind, std::array<double, 6> beta, double ambient, int64_t out_ptr,
-                            bool accumulate) {
+                            bool accumulate, int64_t cap_ptr) {
     DType t = dt_of(dt);
-    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient);
+    const BalanceParams p = bparams(field_ptr, n, (int64_t)dtype_size(t), g, box, src_ptr, cond_ptr, wall, kind, beta, ambient, cap_ptr);
     py::gil_scoped_release nogil;
     cpu::heat_balance(t, p, reinterpret_cast<BalanceSums*>(out_ptr), accumulate);
   }, py::arg("dtype"), py::arg("field_ptr"), py::arg("n"), py::arg("g"), py::arg("box"), py::arg("src_ptr"),
      py::arg("cond_ptr"), py::arg("wall"), py::arg("kind"), py::arg("beta"), py::arg("ambient"), py::arg("out_ptr"),
-     py::arg("accumulate"));
+     py::arg("accumulate"), py::arg("cap_ptr") = 0);
   ck.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
                             std::array<int64_t, 6> box, std::array<double, 3> D, int64_t src_ptr, int64_t cond_ptr,
                             std::array<int64_t, 6> wall, std::array<int, 6> kind, std::array<double, 6> beta,
@@ -997,6 +1013,8 @@ PYBIND11_MODULE(_heat3d, m) {
         for (int f = 0; f < kNumFaces; ++f) flow[py::str(faces[f])] = b.flow[f];
         d["flow"] = flow;
         d["imbalance"] = b.imbalance;
+        // (only while a heat capacity is set: the dict of a run without one keeps its keys)
+        if (b.capacity) d["capacity"] = true;
         return d;
       })
       .def("solve_steady", [](Solver& s, double tol, int64_t max_iter) {
@@ -1082,6 +1100,20 @@ PYBIND11_MODULE(_heat3d, m) {
         s.clear_conductivity();
       })
       .def_property_readonly("has_conductivity", &Solver::has_conductivity)
+      // relative volumetric heat capacity rc >= 1 (global array); values are checked by the solver
+      .def("set_capacity", [](Solver& s, py::array_t<double, py::array::c_style | py::array::forcecast> rc) {
+        const auto& N = s.decomposition().N;
+        if (rc.size() != N[0] * N[1] * N[2])
+          throw UsageError("set_capacity: array size does not match the grid");
+        const double* d = rc.data();
+        py::gil_scoped_release nogil;
+        s.set_capacity(d);
+      }, py::arg("rc"))
+      .def("clear_capacity", [](Solver& s) {
+        py::gil_scoped_release nogil;
+        s.clear_capacity();
+      })
+      .def_property_readonly("has_capacity", &Solver::has_capacity)
       .def_property_readonly("sweeps_active", &Solver::sweeps_active)
       .def_property_readonly("sweeps_overlapped", &Solver::sweeps_overlapped)
       .def_property_readonly("has_source", &Solver::has_source)

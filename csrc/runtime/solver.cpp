@@ -479,6 +479,7 @@ Solver::~Solver() {
       if (f) be_->release(f);
     if (l.source) be_->release(l.source);
     if (l.cond) be_->release(l.cond);
+    if (l.cap) be_->release(l.cap);
     if (l.steady_r) be_->release(l.steady_r);
     if (l.steady_q) be_->release(l.steady_q);
     for (auto& io : l.faces) {
@@ -729,8 +730,8 @@ void Solver::retune() {
   rl_ = false;
   for (bool& b : rl_d_) b = false;
   // a conductivity field: single steps, or the tv sweeps (one shape per
-  // depth, every residual): nothing to time
-  if (has_cond_ || walls_single()) return;
+  // depth, every residual): nothing to time; nor with a heat capacity
+  if (has_cond_ || has_cap_ || walls_single()) return;
   tune_schedules();
   calibrate_remainders();
   // the sweep form is final: its last-residual variant, where one exists
@@ -978,6 +979,7 @@ void Solver::tune_schedules() {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
     set_walls(sp, l);
       sp.box = box;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
@@ -1090,6 +1092,7 @@ void Solver::calibrate_remainders() {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
       sp.state = nullptr;
       sp.cu_reserved = be_->reserved_cus();
@@ -1335,6 +1338,7 @@ int Solver::preheat(int sweeps) {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
     set_walls(sp, l);
       sp.box = l.tb_interior;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
@@ -1434,6 +1438,7 @@ void Solver::enqueue_iteration(int p, int bi) {
     sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
     sp.state = dstate_;
@@ -1549,6 +1554,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
     sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
     set_walls(sp, l);
     sp.box = b;
     for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
@@ -1660,7 +1666,7 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
 }
 
 bool Solver::fused_check() const {
-  return cfg_.fuse_check && be_->is_gpu() && tb_ && !has_cond_ && !tb_overlap_ && local_.size() == 1 &&
+  return cfg_.fuse_check && be_->is_gpu() && tb_ && !has_cond_ && !has_cap_ && !tb_overlap_ && local_.size() == 1 &&
          (comm_->all_local() || comm_->size() == 1) && fake_allreduce_us_ <= 0;
 }
 
@@ -1733,6 +1739,7 @@ void Solver::resolve_coarse() {
       sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
     set_walls(sp, l);
       sp.box = b;
       for (int a = 0; a < 3; ++a) sp.D[a] = phys_.D[a];
@@ -1943,6 +1950,7 @@ void Solver::finalize_converged(int64_t c) {
         sp.L = l.L;
     sp.src = l.source;
     sp.cond = l.cond;
+    sp.cap = l.cap;
         sp.box = l.owned;
         const int64_t w = m - j;
         for (int a = 0; a < 3; ++a) {
@@ -2495,6 +2503,7 @@ HeatBalance Solver::heat_balance() {
     bp.field = l.field[p];
     bp.src = has_source_ ? l.source : nullptr;
     bp.cond = has_cond_ ? l.cond : nullptr;
+    bp.cap = has_cap_ ? l.cap : nullptr;
     bp.L = l.L;
     bp.ambient = cfg_.ambient;
     for (int a = 0; a < 3; ++a) {
@@ -2554,6 +2563,7 @@ HeatBalance Solver::heat_balance() {
       total += r.flow[2 * a + e];
     }
   r.imbalance = total + r.source_power;
+  r.capacity = has_cap_;
   return r;
 }
 

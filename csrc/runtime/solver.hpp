@@ -63,6 +63,7 @@ struct HeatBalance {
   double source_power = 0.0;  // hx hy hz / dt * sum of S (0 without a source)
   double flow[6] = {0, 0, 0, 0, 0, 0};  // x-, x+, y-, y+, z-, z+; positive: into the body
   double imbalance = 0.0;     // sum of the flows + source_power = d(heat)/dt of the scheme
+  bool capacity = false;      // heat is hx hy hz * sum of rc T = T / s (a heat capacity is set)
 };
 
 // Solver::solve_steady's report
@@ -182,6 +183,22 @@ class Solver {
   void set_conductivity_file(const std::string& path);
   void clear_conductivity();
   bool has_conductivity() const { return has_cond_; }
+  // Spatially varying heat capacity, rc T_t = div(alpha c grad T) + q:
+  // `global_rc` is the relative volumetric heat capacity on the global vertex
+  // grid (same shape and order as the source), every value finite and >= 1
+  // (the reference material is the one with the smallest capacity), else every
+  // rank throws UsageError naming the first offending index.  Each local rank
+  // keeps s = dtype(1 / rc) on its owned box plus its full ghost depth, 1 at
+  // the wall vertices and outside the grid (only the centre value of an
+  // updated point is read).  While a capacity is set every iteration runs as a
+  // single step (kernels.hpp cap_update; with walls on refreshed wall planes):
+  // no K-step sweeps, no fused check, no long sweeps, no start-up timing;
+  // Config::cond_sweeps and Config::wall_source_sweeps mean nothing.  Setting
+  // or clearing behaves like set_conductivity.  Not with --compat.
+  void set_capacity(const double* global_rc);
+  void set_capacity_file(const std::string& path);
+  void clear_capacity();
+  bool has_capacity() const { return has_cap_; }
   // K-step sweeps are what run() / step() issue (temporal blocking on, and no
   // conductivity field or Config::cond_sweeps)
   bool sweeps_active() const { return sweeping(); }
@@ -326,6 +343,7 @@ class Solver {
     void* field[3] = {nullptr, nullptr, nullptr};  // nbuf_ of them in use
     void* source = nullptr;  // S = dtype(dt * q) in layout L, allocated by set_source
     void* cond = nullptr;    // Ch = dtype(0.5 * c) in layout L, allocated by set_conductivity
+    void* cap = nullptr;     // s = dtype(1 / rc) in layout L, allocated by set_capacity
     void* steady_r = nullptr;  // solve_steady: residual and A p, in layout L, allocated on first use
     void* steady_q = nullptr;
     Box owned, interior;
@@ -357,12 +375,13 @@ class Solver {
   bool initialized_ = false;
   void preflight_source();
   bool has_cond_ = false;
-  // K-step sweeps run (temporal blocking on, and no conductivity field or the
-  // tv sweeps asked for)
-  bool sweeping() const { return tb_ && (!has_cond_ || cond_sweeping()) && !walls_single(); }
+  bool has_cap_ = false;
+  // K-step sweeps run (temporal blocking on, no heat capacity, and no
+  // conductivity field or the tv sweeps asked for)
+  bool sweeping() const { return tb_ && !has_cap_ && (!has_cond_ || cond_sweeping()) && !walls_single(); }
   // ... of the tv family, with the conductivity field (--conductivity-sweeps)
   // (behind walls too: the wall forms of the tv kernels)
-  bool cond_sweeping() const { return tb_ && has_cond_ && cfg_.cond_sweeps && Kc_ >= 2; }
+  bool cond_sweeping() const { return tb_ && has_cond_ && !has_cap_ && cfg_.cond_sweeps && Kc_ >= 2; }
   // Insulated walls (Config::insulated).  Sweeps run the wall forms of the
   // lean kernel (StencilParams::wall: the substitution happens in the kernel,
   // at every stage).  Single steps run the kernels as they are on wall planes
@@ -383,7 +402,8 @@ class Solver {
   unsigned walls_ = 0, conv_ = 0;
   double conv_beta_[6] = {-1, -1, -1, -1, -1, -1};
   bool walls_single() const {
-    return walls_ && (has_cond_ ? !cond_sweeping() : has_source_ && !cfg_.wall_source_sweeps);
+    // (a heat capacity: single steps whatever else is set)
+    return walls_ && (has_cap_ || (has_cond_ ? !cond_sweeping() : has_source_ && !cfg_.wall_source_sweeps));
   }
   // the form of this run's sweeps: a source or not, behind which kind of wall
   SweepForm sweep_form() const {
@@ -413,6 +433,7 @@ class Solver {
   void set_source_rows(const GlobalRows& rows);
   void set_field_rows(const GlobalRows& rows);
   void set_conductivity_rows(const GlobalRows& rows);
+  void set_capacity_rows(const GlobalRows& rows);
   void scatter_global(const GlobalRows& rows, double scale, const Local& l, void* const* bufs, int nbufs);
   void consolidate_fields();
   // Start-up canary of the per-stream graphs (initialize(), every rank at the

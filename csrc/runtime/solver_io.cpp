@@ -419,6 +419,8 @@ void Solver::save_checkpoint(const std::string& dir) {
     j.set_raw("has_source", has_source_ ? "true" : "false");
     // nor the conductivity field
     j.set_raw("has_conductivity", has_cond_ ? "true" : "false");
+    // nor the heat capacity
+    j.set_raw("has_capacity", has_cap_ ? "true" : "false");
     j.set("insulated", insulated_str(walls_ & ~conv_));
     // (only runs with a convective face write these keys)
     if (conv_) {
@@ -455,6 +457,10 @@ void Solver::load_checkpoint(const std::string& dir) {
   HEAT3D_CHECK(!(meta.count("has_conductivity") && meta["has_conductivity"] == "true") || has_cond_,
                "checkpoint " << dir << " was written with a conductivity field, which is not stored in it: set it "
                                        "again (set_conductivity / --conductivity) before loading it");
+  // (checkpoints older than the heat capacity have no such key)
+  HEAT3D_CHECK(!(meta.count("has_capacity") && meta["has_capacity"] == "true") || has_cap_,
+               "checkpoint " << dir << " was written with a heat capacity, which is not stored in it: set it "
+                                       "again (set_capacity / --capacity) before loading it");
   // (checkpoints older than the insulated walls have no such key: all Dirichlet)
   {
     const std::string was = meta.count("insulated") ? meta["insulated"] : std::string("none");
@@ -751,6 +757,104 @@ void Solver::clear_conductivity() {
     l.cond = nullptr;
   }
   has_cond_ = false;
+  set_cond_depth();
+  if (!initialized_) return;
+  consolidate_fields();
+  retune();  // the K-step sweeps are back: timed as at initialize()
+  reset_state(false);
+}
+
+void Solver::set_capacity_file(const std::string& path) {
+  const int fd = open_global_file(path, dec_.N, "--capacity");
+  try {
+    set_capacity_rows(rows_of_file(fd));
+  } catch (...) {
+    io::close_raw(fd);
+    throw;
+  }
+  io::close_raw(fd);
+}
+
+void Solver::set_capacity(const double* global_rc) { set_capacity_rows(rows_of_array(global_rc)); }
+
+void Solver::set_capacity_rows(const GlobalRows& rows) {
+  if (cfg_.compat || cfg_.scheme == "reference")
+    throw UsageError("a heat capacity is not part of --compat / --scheme reference (the reference's uniform material)");
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  std::size_t extra = 0;
+  for (const auto& l : local_)
+    if (!l.cap) extra += l.L.bytes();
+  preflight_extra_field("heat capacity", extra);
+  // every value this process reads (its boxes and their ghost depth) must be
+  // finite and >= 1; the first offending global index is kept for the message
+  const int64_t* N = dec_.N;
+  unsigned long long bad = 0;
+  int64_t first = -1;
+  const GlobalRows checked = [&rows, &bad, &first, N](int64_t gi, int64_t gj, int64_t gk, int64_t n, double* dst) {
+    rows(gi, gj, gk, n, dst);
+    const bool wall_row = gi == 0 || gi == N[0] - 1 || gj == 0 || gj == N[1] - 1;
+    for (int64_t k = 0; k < n; ++k) {
+      const double rc = dst[k];
+      if (!(rc >= 1.0 && rc <= 1.7976931348623157e308)) {  // NaN fails both
+        ++bad;
+        const int64_t at = (gi * N[1] + gj) * N[2] + gk + k;
+        if (first < 0 || at < first) first = at;
+      }
+      // s = 1 / rc in double (rounded to the dtype by the scatter); the wall
+      // vertices hold 1: they are never updated
+      const bool wall = wall_row || gk + k == 0 || gk + k == N[2] - 1;
+      dst[k] = wall ? 1.0 : 1.0 / rc;
+    }
+  };
+  for (auto& l : local_) {
+    if (!l.cap) l.cap = be_->alloc(l.L.bytes());
+    void* bufs[1] = {l.cap};
+    scatter_global(checked, 1.0, l, bufs, 1);
+  }
+  // one decision for the job: no rank throws alone while its peers go on
+  bad = allreduce_sum_u64(bad);
+  if (bad) {
+    has_cap_ = true;  // (the buffers exist)
+    clear_capacity();
+    // the first offending index of the job: the smallest any rank read (a max of the complements)
+    unsigned long long key = first < 0 ? 0ull : ~(unsigned long long)first;
+    if (!comm_->all_local() && comm_->size() > 1) {
+      void* d = be_->alloc(8);
+      be_->copy(d, &key, 8, CopyKind::H2D, kReduce);
+      comm_->allreduce(d, 1, RedType::U64, RedOp::Max, *be_, kReduce);
+      be_->copy(&key, d, 8, CopyKind::D2H, kReduce);
+      be_->sync(kReduce);
+      be_->release(d);
+    }
+    first = (int64_t)~key;
+    const std::string where = "(" + std::to_string(first / (N[1] * N[2])) + ", " +
+                              std::to_string(first / N[2] % N[1]) + ", " + std::to_string(first % N[2]) + ")";
+    throw UsageError("capacity: " + std::to_string(bad) + " value(s) are not finite and >= 1, the first at index " +
+                     where + " (relative heat capacity rc = rho c_p / min(rho c_p); the time step is that of the "
+                     "material with the smallest capacity); no heat capacity is set");
+  }
+  has_cap_ = true;
+  set_cond_depth();
+  if (!initialized_) return;
+  consolidate_fields();
+  retune();
+  reset_state(false);
+}
+
+void Solver::clear_capacity() {
+  if (!has_cap_) return;
+  be_->sync_all();
+  destroy_graphs();
+  pending_.valid = false;
+  for (auto& l : local_) {
+    if (!l.cap) continue;
+    planned_bytes_ -= std::min(planned_bytes_, l.L.bytes());
+    be_->release(l.cap);
+    l.cap = nullptr;
+  }
+  has_cap_ = false;
   set_cond_depth();
   if (!initialized_) return;
   consolidate_fields();

@@ -85,6 +85,33 @@ class HeatEquation3D:
         c = np.where(y < float(split), float(c_low), float(c_high))
         return np.broadcast_to(c[None, :, None], self.n).copy()
 
+    def layered_capacity(self, rc_low: float, rc_high: float, split: float = 0.5) -> np.ndarray:
+        """Two-layer body: relative volumetric heat capacity rc = ``rc_low`` where
+        y_j < ``split``, ``rc_high`` elsewhere (global array, rc >= 1), the layers
+        of ``layered_conductivity``."""
+        y = np.arange(self.n[1], dtype=np.float64) * self.h[1]
+        rc = np.where(y < float(split), float(rc_low), float(rc_high))
+        return np.broadcast_to(rc[None, :, None], self.n).copy()
+
+    def dirichlet_mode(self, m: Sequence[int], s: float = 1.0) -> Tuple[np.ndarray, float]:
+        """Discrete eigenmode of the update between Dirichlet walls at 0: the
+        product of sin(pi m_a i_a / (N_a - 1)) over the three axes (global array,
+        0 on every wall vertex).  One step of a body with the uniform capacity
+        factor ``s`` = 1 / rc multiplies it by the returned factor
+        g = 1 - s * 4 sum_a D_a sin^2(pi m_a / (2 (N_a - 1))); ``s`` = 1 is the
+        body without a heat capacity."""
+        v = []
+        lam = 0.0
+        for a in range(3):
+            N = self.n[a]
+            i = np.arange(N, dtype=np.float64)
+            va = np.sin(np.pi * m[a] * i / (N - 1))
+            va[0] = va[-1] = 0.0
+            v.append(va)
+            lam += self.D[a] * np.sin(np.pi * m[a] / (2.0 * (N - 1))) ** 2
+        T = v[0][:, None, None] * v[1][None, :, None] * v[2][None, None, :]
+        return T, float(1.0 - float(s) * 4.0 * lam)
+
     def layered_steady(self, c: np.ndarray) -> np.ndarray:
         """Exact steady state of the discrete scheme for a conductivity that
         varies in y only, between the walls T(y=0) = 0 and T(y=1) = 1: a
@@ -404,6 +431,30 @@ class HeatSolver:
         """Back to the uniform material (and the K-step sweeps)."""
         self._s.clear_conductivity()
 
+    def set_capacity(self, rc) -> None:
+        """Spatially varying heat capacity: rc T_t = div(alpha c grad T) + q, ``rc``
+        the relative volumetric heat capacity rho c_p on the global vertex grid,
+        rc >= 1 (the reference material is the one with the smallest capacity, so
+        the time step stays stable).  A value below 1 or not finite is the native
+        ``UsageError`` (a RuntimeError) naming the first offending index, raised
+        on every rank.  While set, every iteration runs as a single step
+        (``conductivity_sweeps`` and ``wall_source_sweeps`` mean nothing), the
+        stored heat of ``heat_balance()`` is weighted with rc, and the steady
+        state (``solve_steady``) is the one without a capacity.  A body with
+        rc == 1 everywhere agrees with one without a capacity to rounding, not
+        bitwise.  Keeps the field, restarts the iteration count and the
+        convergence state at 0.  Collective."""
+        rc = np.ascontiguousarray(np.asarray(rc, dtype=np.float64))
+        if rc.shape != tuple(self.model.n):
+            raise ValueError(f"set_capacity: shape {rc.shape} != grid {tuple(self.model.n)}")
+        self._ensure()
+        self._s.set_capacity(rc)
+
+    def clear_capacity(self) -> None:
+        """Back to one capacity everywhere: the schedule and the bits of a run
+        that never had one."""
+        self._s.clear_capacity()
+
     def set_field(self, T) -> None:
         """User initial condition with its Dirichlet data: the boundary vertices
         of ``T`` (global shape) become the fixed wall values, its interior T^0;
@@ -442,7 +493,7 @@ class HeatSolver:
     def heat_balance(self) -> Dict:
         """Where the heat is and where it goes, summed on the device over the
         updated points (global indices 1 .. N - 2) of the current field: ``heat``
-        (hx hy hz sum T), ``t_min`` / ``t_max`` (NaNs ignored), ``nonfinite`` (the
+        (hx hy hz sum T; with a heat capacity hx hy hz sum rc T, and the dict then has ``capacity``: True), ``t_min`` / ``t_max`` (NaNs ignored), ``nonfinite`` (the
         count of NaN / Inf values), ``flow`` per face ``{"x-": ..., ...}`` (positive:
         into the body; exactly 0.0 on an insulated face), ``source_power`` and
         ``imbalance``, the sum of the flows and the source power: the rate of

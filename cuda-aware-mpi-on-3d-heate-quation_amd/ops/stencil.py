@@ -94,6 +94,16 @@ def _cond_ptr(src: PaddedField, conductivity: Optional[PaddedField]) -> int:
     return conductivity.data_ptr()
 
 
+def _cap_ptr(src: PaddedField, cap: Optional[PaddedField]) -> int:
+    """Pointer of the heat-capacity field s = dtype(1 / rc) (0: one capacity
+    everywhere); same layout, dtype and device as the field."""
+    if cap is None:
+        return 0
+    if cap.layout != src.layout or cap.dtype != src.dtype or cap.device != src.device:
+        raise ValueError("the capacity field must share the field's layout, dtype and device")
+    return cap.data_ptr()
+
+
 FACES = ("x-", "x+", "y-", "y+", "z-", "z+")
 
 
@@ -154,8 +164,19 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
               state: Optional[torch.Tensor] = None, slot: int = 0,
               source: Optional[PaddedField] = None,
               conductivity: Optional[PaddedField] = None,
-              walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> None:
+              walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0,
+              cap: Optional[PaddedField] = None) -> None:
     """dst[box] = FTCS(src) on the owned box (default: all owned points).
+
+    The fields may have deep ghosts (``PaddedField(gx=, gy=, gz=)``): the kernels
+    index them with their own ghost depths (one ghost layer, the default, is
+    the layout this entry always used).
+
+    ``cap``: optional field s = dtype(1 / rc), rc >= 1 the relative volumetric
+    heat capacity, in the same layout (only the centre value of an updated
+    point is read): the update becomes kernels.hpp cap_update on the increment
+    of the step, T' = fma(s, u, T) (its own gfx950 kernels, stencil_cap.hip),
+    with or without ``source`` and ``conductivity``.
 
     ``walls``: insulated walls as ``wall_coords`` gives them (CPU tensors only,
     with or without a source or a conductivity: the single-step gfx950
@@ -190,15 +211,17 @@ def ftcs_step(src: PaddedField, dst: PaddedField, D: Sequence[float],
     ext = native()
     qptr = _source_ptr(src, source)
     cptr = _cond_ptr(src, conductivity)
+    kptr = _cap_ptr(src, cap)
+    g = [src.gx, src.gy, src.gz]
     if src.device.type == "cuda":
         if walls is not None:
             raise ValueError("the single-step gfx950 kernels take no walls (copy the wall planes first)")
         ext.hip.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot,
-                        kernel, _stream_ptr(src.flat), qptr, cptr)
+                        kernel, _stream_ptr(src.flat), qptr, cptr, kptr, g)
     else:
         w = list(walls) if walls is not None else [ext.NO_WALL] * 6
         ext.cpu.stencil(src.dt, src.data_ptr(), dst.data_ptr(), list(n), b, list(D), sptr, slot, qptr, cptr, w,
-                        convective_faces(conv), float(ambient))
+                        convective_faces(conv), float(ambient), kptr, g)
 
 
 def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: str = "auto",
@@ -227,7 +250,7 @@ def ftcs_step2(src: PaddedField, dst: PaddedField, D: Sequence[float], kernel: s
 def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int],
           ux: Sequence[int] = (0, -1), kernel: str = "tl3", state: Optional[torch.Tensor] = None,
           slot: int = 0, source: Optional[PaddedField] = None,
-          conductivity: Optional[PaddedField] = None) -> None:
+          conductivity: Optional[PaddedField] = None, cap: Optional[PaddedField] = None) -> None:
     """One K-step sweep (K from ``kernel``: tl2..tl6) on ``box``
     = (x0, x1, y0, y1, z0, z1) of a deep-ghost field, with the intermediate
     steps computed on the x range ``ux`` (the solver's x-slab schedule).
@@ -237,7 +260,9 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
     field Ch = dtype(0.5 * c) in the same layout; on the GPU it needs a ``tv2``
     / ``tv3`` kernel (stencil_tbv.hip; the tl kernels have no conductivity form
     and a tv kernel needs one: RuntimeError either way), CPU tensors run the
-    K-single-steps definition with it."""
+    K-single-steps definition with it.  ``cap``: the heat-capacity field
+    s = dtype(1 / rc) in the same layout: CPU tensors run K single steps with it
+    (the definition); no gfx950 sweep kernel has a capacity form (RuntimeError)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -250,15 +275,16 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
     qptr = _source_ptr(src, source)
     cptr = _cond_ptr(src, conductivity)
     if src.device.type == "cuda":
-        native().hip.stencil_sweep(*args, _stream_ptr(src.flat), qptr, cptr)
+        native().hip.stencil_sweep(*args, _stream_ptr(src.flat), qptr, cptr, _cap_ptr(src, cap))
     else:
-        native().cpu.stencil_sweep(*args, qptr, cptr)
+        native().cpu.stencil_sweep(*args, qptr, cptr, _cap_ptr(src, cap))
 
 
 def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[int], u: Sequence[int],
            kernel: str = "tl3", state: Optional[torch.Tensor] = None, slot: int = 0,
            source: Optional[PaddedField] = None, conductivity: Optional[PaddedField] = None,
-           walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> None:
+           walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0,
+           cap: Optional[PaddedField] = None) -> None:
     """K-step sweep with deep ghosts on every axis (the block-decomposition
     schedule): ``u`` = (ux0, ux1, uy0, uy1, uz0, uz1) are the update ranges of
     the intermediate steps.  GPU tensors run the lean kernel, CPU tensors the
@@ -275,7 +301,8 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     single steps with both on CPU tensors.  ``walls`` together with
     ``conductivity`` (and a ``tv2`` / ``tv3`` kernel): the wall forms of the tv
     sweep (stencil_tbv_wall.hip / stencil_tbv_conv.hip, with or without a source)
-    on GPU tensors, K single steps with them on CPU tensors."""
+    on GPU tensors, K single steps with them on CPU tensors.  ``cap``: as in
+    ``sweep`` (CPU tensors only; the gfx950 sweep kernels refuse it)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
@@ -289,9 +316,10 @@ def sweep3(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence
     cptr = _cond_ptr(src, conductivity)
     w = list(walls) if walls is not None else [native().NO_WALL] * 6
     if src.device.type == "cuda":
-        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr, w, convective_faces(conv), float(ambient))
+        native().hip.stencil_sweep3(*args, _stream_ptr(src.flat), qptr, cptr, w, convective_faces(conv), float(ambient),
+                                    _cap_ptr(src, cap))
     else:
-        native().cpu.stencil_sweep3(*args, qptr, cptr, w, convective_faces(conv), float(ambient))
+        native().cpu.stencil_sweep3(*args, qptr, cptr, w, convective_faces(conv), float(ambient), _cap_ptr(src, cap))
 
 
 def _face_scale(physics, axis: int) -> float:
@@ -322,7 +350,8 @@ def _unkey(k: int) -> float:
 
 def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = None,
                  source: Optional[PaddedField] = None, cond: Optional[PaddedField] = None,
-                 walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0) -> dict:
+                 walls: Optional[Sequence[int]] = None, conv=None, ambient: float = 0.0,
+                 cap: Optional[PaddedField] = None) -> dict:
     """Heat balance of ``box`` (default: all owned points) of a field whose block
     is the interior of its grid: every face of the box lies next to a wall.
 
@@ -332,6 +361,8 @@ def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = Non
     vertex outside the box); ``conv``: the convective ones among them
     (``convective_faces`` forms) with the ambient temperature ``ambient``.
     ``source``: S = dtype(dt q), ``cond``: Ch = dtype(0.5 c), in the field's layout.
+    ``cap``: s = dtype(1 / rc) in the field's layout: the stored heat becomes
+    hx hy hz sum T / s (each term a float64 quotient); nothing else changes.
 
     GPU tensors run the gfx950 kernel (heat_balance.hip) on torch's current
     stream, CPU tensors the definition (cpu::heat_balance).  Returns the dict of
@@ -357,15 +388,16 @@ def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = Non
     beta = [max(v, 0.0) for v in beta]
     qptr = _source_ptr(field, source)
     cptr = _cond_ptr(field, cond)
+    kptr = _cap_ptr(field, cap)
     out = torch.zeros(ext.BALANCE_SUMS_BYTES // 8, dtype=torch.int64, device=field.device)
     args = (field.dt, field.data_ptr(), list(n), [field.gx, field.gy, field.gz], b, qptr, cptr, wall, kind, beta,
             float(ambient))
     if field.device.type == "cuda":
         scratch = torch.empty(ext.BALANCE_SCRATCH_BYTES // 8, dtype=torch.int64, device=field.device)
-        ext.hip.heat_balance(*args, scratch.data_ptr(), out.data_ptr(), False, _stream_ptr(field.flat))
+        ext.hip.heat_balance(*args, scratch.data_ptr(), out.data_ptr(), False, _stream_ptr(field.flat), kptr)
         raw = out.cpu()
     else:
-        ext.cpu.heat_balance(*args, out.data_ptr(), False)
+        ext.cpu.heat_balance(*args, out.data_ptr(), False, kptr)
         raw = out
     hi, lo = raw[:8].view(torch.float64), raw[8:16].view(torch.float64)
     sums = [float(hi[q]) + float(lo[q]) for q in range(8)]  # the final rounding
@@ -377,9 +409,12 @@ def heat_balance(field: PaddedField, physics, box: Optional[Sequence[int]] = Non
         flow[name] = 0.0 if kind[f] == 1 else _face_scale(physics, f // 2) * sums[2 + f]
         total += flow[name]
     source_power = vol / dt * sums[1] if source is not None else 0.0
-    return {"heat": vol * sums[0], "t_min": _unkey(int(raw[16])), "t_max": _unkey(int(raw[17])),
-            "nonfinite": int(raw[18]), "source_power": source_power, "flow": flow,
-            "imbalance": total + source_power}
+    out = {"heat": vol * sums[0], "t_min": _unkey(int(raw[16])), "t_max": _unkey(int(raw[17])),
+           "nonfinite": int(raw[18]), "source_power": source_power, "flow": flow,
+           "imbalance": total + source_power}
+    if cap is not None:  # (as HeatSolver.heat_balance: the key appears with a capacity only)
+        out["capacity"] = True
+    return out
 
 
 def _steady_check(*fields: PaddedField) -> PaddedField:
