@@ -44,7 +44,12 @@
 //     masked step restricted to the same cone.  An edge wave publishes the
 //     one LDS row its neighbour reads and holds the same barrier.  The three
 //     roles branch once per wave, never per step, which keeps each loop's
-//     live registers its own;
+//     live registers its own.  The edge-role kernels also have a z-masked
+//     step (StepForm below: the mask-free step with the stage outputs selected
+//     by the lane's z condition) for the y-free waves of a tile that has
+//     columns outside the z update range, skip the stages of the masked step
+//     that the pipeline fill of a piece has not reached, and leave the padded
+//     steps after a piece's last plane unrun;
 //   * loads are an SGPR row base plus one lane offset (global_load saddr
 //     form), clamped rows / planes fold into the SGPR base.
 //
@@ -129,6 +134,15 @@ __device__ __forceinline__ void buf_store(Real v, __amdgpu_buffer_rsrc_t r, unsi
   else
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, AUX);
 }
+
+// The form of one plane step of the lean kernel (stencil_tbl_kernel.inc step()):
+// kStepMasked evaluates every x / y / z condition; kStepFree none (a wave whose
+// rows, columns and stage planes are all updated, counted and stored);
+// kStepZ (edge-role kernels) the z conditions only: a wave and plane step that
+// would be mask-free in a tile that has columns outside the z update range.
+enum StepForm : int { kStepMasked = 0, kStepFree = 1, kStepZ = 2 };
+template <int F>
+using step_form = std::integral_constant<int, F>;
 
 // f(integral_constant<int, I>) for I = B .. E-1, unrolled at compile time
 template <int B, int E, typename Fn>

@@ -239,15 +239,21 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
     for (int i = 0; i < NPRE; ++i) load_plane(x0 - 1 + i, q[i]);
   }
 
-  // One plane step.  FAST: every condition below is known true.  ROLE: 0 an
+  // One plane step.  FORM (impl.hpp StepForm): kStepFree, every condition below
+  // is known true; kStepZ (edge-role kernels only), the x and y conditions are
+  // known true and the lanes outside the z update range pass their centre value
+  // on; kStepMasked, every condition is evaluated.  ROLE: 0 an
   // interior wave (R rows, every stage); 1 / 2 the edge role of wave 0 /
   // WY - 1: RB rows, and of row r only the stages inside the tile's cone
   // (static, so the stage rings outside it are never allocated).  The stage-s
   // output of tile row rp is read only by stage s + 1 of rows rp - 1 .. rp + 1,
   // and stage s is valid on rows [s + 1, TY - s - 1): everything a cone value
   // reads is in the cone, whatever the masks say.
-  auto step = [&](auto fast_tag, const int x, auto ph_tag, auto role_tag) {
-    constexpr bool FAST = decltype(fast_tag)::value;
+  auto step = [&](auto form_tag, const int x, auto ph_tag, auto role_tag) {
+    constexpr int FORM = decltype(form_tag)::value;
+    constexpr bool FAST = FORM != kStepMasked;  // no x / y condition is evaluated
+    constexpr bool ZSEL = FORM == kStepZ;
+    static_assert(!ZSEL || EDGE, "the z-masked step exists in the edge-role kernels only");
     constexpr int ph = decltype(ph_tag)::value;
     constexpr int ROLE = decltype(role_tag)::value;
     constexpr int NR = ROLE ? RB : R;
@@ -272,6 +278,27 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
     const int wl = max(wave - 1, 0), wh = min(wave + 1, WY - 1);
 #pragma unroll
     for (int s = 0; s < K; ++s) {
+      if constexpr (EDGE && !FAST) {
+        // Dead stage of the pipeline fill (uniform: one scalar branch).  The
+        // piece stores planes [xa, xe) at stage K - 1, and the stage-s output of
+        // plane p is read only by stage s + 1 of planes p - 1 .. p + 1, so the
+        // piece needs stage s on the planes p >= xa - (K - 1 - s) = x0 + s only
+        // (the cone along x).  Stage s meets plane p at step p + s: before step
+        // x0 + 2s its plane is below that cone.  Such a stage counts and stores
+        // nothing (xcnt asks for x >= x0 + 2s; the first stored plane xa meets
+        // stage K - 1 at step x0 + 2(K - 1)), and what it would write, stage
+        // s + 1's input on a plane below x0 + s, is read by no needed stage:
+        // stage s + 1 is needed from step x0 + 2s + 2 on, where its plane is
+        // x0 + s + 1 or above and its lowest input plane x0 + s.  Everything a
+        // cone value reads is in the cone, so the stage's rows are skipped and
+        // its ring slot keeps whatever it held; the stages that would read that
+        // are dead themselves.  Stage 0 is never dead, so the ring load below
+        // it is not skipped; the rows published above and the barrier are those
+        // of every step.  (The other end has no dead stage: every stage meets
+        // the last plane it needs, xe - 1 + (K - 1 - s), at step xlast; the
+        // padded steps after xlast are left by the caller.)
+        if (s > 0 && x < x0 + 2 * s) continue;
+      }
       Real(&M)[RB] = s == 0 ? q[sM] : f[s > 0 ? s - 1 : 0][fm];
       Real(&C)[RB] = s == 0 ? q[sC] : f[s > 0 ? s - 1 : 0][fc];
       Real(&P)[RB] = s == 0 ? q[sP] : f[s > 0 ? s - 1 : 0][fw];
@@ -365,11 +392,14 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
         }
         if (s < K - 1) {
           Real(&N)[RB] = f[s < K - 1 ? s : 0][fw];
-          if constexpr (FAST) N[r] = nv;
+          if constexpr (ZSEL) N[r] = zin ? nv : C[r];
+          else if constexpr (FAST) N[r] = nv;
           else N[r] = (upd && zin) ? nv : C[r];
         }
         if (!RL || s == K - 1) {
           if constexpr (FAST) {
+            // (kStepZ too: cnt has no lane term in any form; the lanes outside
+            // the z update range are dropped once, by `ok` at the end)
             m[s] = fmax(m[s], d);
           } else {
             if (cnt) m[s] = fmax(m[s], d);
@@ -394,7 +424,15 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
 
   // whole chunks of U steps (the unrolled body needs a constant trip count);
   // padded steps past xlast take the masked form and count / store nothing
-  auto run = [&](auto role_tag, const bool fast) {
+  // (without the edge role; with it they are not run)
+  // (edge-role kernels: `yfree`, the wave's rows need no y condition.  With
+  // zfast that is the mask-free step; in a tile that has columns outside the z
+  // update range it is the z-masked step, on the same plane steps [xf_lo, xf_hi],
+  // whose bounds hold x terms only.  A padded step past xlast has nothing to
+  // count, store or pass on, and no step follows it: the chunk is left there,
+  // by every wave of the workgroup alike, so no barrier is left half taken.)
+  auto run = [&](auto role_tag, const bool yfree) {
+    const bool fast = yfree && zfast, zonly = yfree && !zfast;
     if constexpr (EDGE) {
       // the rings are set up per role: nothing of one role's loop is live in another's
       constexpr int NR = decltype(role_tag)::value ? RB : R;
@@ -412,8 +450,11 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
       static_for<0, U>([&](auto ph_tag) {
         constexpr int ph = decltype(ph_tag)::value;
         const int x = xb + ph;
-        if (fast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag, role_tag);
-        else step(std::false_type{}, x, ph_tag, role_tag);
+        if (x > xlast) return;
+        const bool xfree = x >= xf_lo && x <= xf_hi;
+        if (fast && xfree) step(step_form<kStepFree>{}, x, ph_tag, role_tag);
+        else if (zonly && xfree) step(step_form<kStepZ>{}, x, ph_tag, role_tag);
+        else step(step_form<kStepMasked>{}, x, ph_tag, role_tag);
       });
     }
   };
@@ -422,17 +463,18 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBL_NAME(const Real* __restrict__
     // the register rows of the other role dead in each loop).  Mask-free
     // where every row is inside the box and the update range: then every
     // cone value is updated, counted and (owned rows, last stage) stored.
-    const bool efast = zfast && yb >= max(g.uylo, g.blo[1]) && yb + RB <= min(g.uyhi, g.bhi[1]);
-    if (wave == 0) run(std::integral_constant<int, 1>{}, efast);
-    else if (wave == WY - 1) run(std::integral_constant<int, 2>{}, efast);
-    else run(std::integral_constant<int, 0>{}, wfast);
+    // (The y part of that, and of wfast; run() adds the tile's z part.)
+    const bool erows = yb >= max(g.uylo, g.blo[1]) && yb + RB <= min(g.uyhi, g.bhi[1]);
+    if (wave == 0) run(std::integral_constant<int, 1>{}, erows);
+    else if (wave == WY - 1) run(std::integral_constant<int, 2>{}, erows);
+    else run(std::integral_constant<int, 0>{}, wrows);
   } else {
     for (int xb = x0; xb <= xlast; xb += U) {
       static_for<0, U>([&](auto ph_tag) {
         constexpr int ph = decltype(ph_tag)::value;
         const int x = xb + ph;
-        if (wfast && x >= xf_lo && x <= xf_hi) step(std::true_type{}, x, ph_tag, std::integral_constant<int, 0>{});
-        else step(std::false_type{}, x, ph_tag, std::integral_constant<int, 0>{});
+        if (wfast && x >= xf_lo && x <= xf_hi) step(step_form<kStepFree>{}, x, ph_tag, std::integral_constant<int, 0>{});
+        else step(step_form<kStepMasked>{}, x, ph_tag, std::integral_constant<int, 0>{});
       });
     }
   }
