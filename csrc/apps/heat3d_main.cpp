@@ -195,6 +195,7 @@ static int drive(const Config& cfg, Solver& solver) {
     j.set("kernel", solver.kernel_name());
     j.set_bool("has_capacity", solver.has_capacity());
     j.set_bool("conductivity_sweeps", cfg.cond_sweeps);
+    j.set_bool("capacity_sweeps", cfg.cap_sweeps);
     j.set_bool("wall_source_sweeps", cfg.wall_source_sweeps);
     j.set("insulated", insulated_str(cfg.insulated));
     j.set("convective", convective_str(cfg.convective));

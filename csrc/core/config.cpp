@@ -209,6 +209,9 @@ std::string Config::usage() {
      << "  --ambient T               the ambient temperature T_inf of the convective walls (default 0)\n"
      << "  --conductivity-sweeps     with a conductivity field: K-step sweeps of the tv kernels (tv2 / tv3,\n"
      << "                            depth min(K, 3)) instead of single steps; same bits (not with --compat)\n"
+     << "  --capacity-sweeps         with a heat capacity and a conductivity field: K-step sweeps of the tc kernels\n"
+     << "                            (tc2 / tc3, depth min(K, 3)) instead of single steps; same bits; without a\n"
+     << "                            conductivity it does nothing (not with --compat)\n"
      << "  --wall-source-sweeps      with insulated or convective walls and a heat source: K-step sweeps of the\n"
      << "                            wall forms with a source instead of single steps; same bits (not with --compat)\n"
      << "  --heat-balance            after the run report: stored heat, temperature range, heat flow through each\n"
@@ -367,6 +370,7 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--conductivity") c.conductivity_file = get("--conductivity");
     else if (key == "--capacity") c.capacity_file = get("--capacity");
     else if (key == "--conductivity-sweeps") c.cond_sweeps = true;
+    else if (key == "--capacity-sweeps") c.cap_sweeps = true;
     else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
     else if (key == "--heat-balance") c.heat_balance = true;
     else if (key == "--steady-solve") c.steady_solve = true;
@@ -509,6 +513,8 @@ Config Config::parse(int argc, const char* const* argv) {
                      insulated_str(convective_mask(c.convective) & c.insulated));
   if (c.cond_sweeps && c.compat)
     throw UsageError("--conductivity-sweeps is not part of --compat (the reference's uniform material)");
+  if (c.cap_sweeps && c.compat)
+    throw UsageError("--capacity-sweeps is not part of --compat (the reference's uniform material)");
   if (c.heat_balance && (c.compat || c.scheme == "reference"))
     throw UsageError("--heat-balance is not part of --compat / --scheme reference (the reference's report)");
   if (c.steady_solve) {

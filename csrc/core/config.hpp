@@ -69,6 +69,10 @@ struct Config {
   // --conductivity-sweeps: with a conductivity field, K-step sweeps of the tv
   // kernel family (stencil_tbv.hip) instead of single steps.  Off by default.
   bool cond_sweeps = false;
+  // --capacity-sweeps: with a heat capacity and a conductivity field, K-step
+  // sweeps of the tc kernel family (stencil_tbc.hip) instead of single steps.
+  // Off by default; with a capacity but no conductivity it does nothing.
+  bool cap_sweeps = false;
   // --wall-source-sweeps: with insulated or convective walls and a heat source,
   // K-step sweeps of the lean kernel's wall forms with a source
   // (stencil_tbl_wall_src.hip, stencil_tbl_conv_src.hip) instead of single

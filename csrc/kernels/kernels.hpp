@@ -28,8 +28,9 @@ struct KernelSpec {
   // register-ring sweep kernels (tb2 / tbK / trK) were retired in round 3:
   // no default path used them (docs/PERFORMANCE.md keeps their numbers).
   // TBV: the K-step sweep with a conductivity field (stencil_tbv.hip; spec
-  // tv2 / tv3), one shape per dtype and depth.
-  enum Kind { Naive = 0, Tile = 2, TBL = 6, TBV = 7 } kind = Tile;
+  // tv2 / tv3), one shape per dtype and depth.  TBC: the tv sweep with a heat
+  // capacity as well (stencil_tbc.hip; spec tc2 / tc3).
+  enum Kind { Naive = 0, Tile = 2, TBL = 6, TBV = 7, TBC = 8 } kind = Tile;
   int K = 0;  // multi-step kinds: time steps per sweep
   int WZ = 0, WY = 0;  // waves per workgroup along z and y
   int V = 0;  // elements per lane along z (0 = default for dtype)
@@ -39,7 +40,7 @@ struct KernelSpec {
   int NT = 0; // TBL: T^n ring size
   int ZS = 0; // TBL: tile stride along z (stored columns per tile; 0 = chosen per box)
   int EW = 0; // TBL: edge role of a tile's two halo waves (0 = off, else 1 + the rows each also owns)
-  bool multi_step() const { return kind == TBL || kind == TBV; }
+  bool multi_step() const { return kind == TBL || kind == TBV || kind == TBC; }
   static KernelSpec parse(const std::string& s);
   std::string str() const;
   // zero (default) fields replaced by the tuned defaults for dtype t
@@ -138,8 +139,10 @@ struct StencilParams {
   // (steady_increment / steady_increment_var, plus the source) scaled by s in
   // one fused multiply-add onto the centre value.  nullptr: one capacity
   // everywhere, the kernels above.  Honoured by cpu::stencil / stencil_multi
-  // (with `wall` / `wall_beta` too) and by the single-step gfx950 kernels of
-  // stencil_cap.hip (hip::stencil dispatches there); every other gfx950
+  // (with `wall` / `wall_beta` too), by the single-step gfx950 kernels of
+  // stencil_cap.hip (hip::stencil dispatches there) and, together with `cond`,
+  // by the tc sweeps (stencil_tbc.hip: the values on the ghost layers an update
+  // range reaches must then be the neighbours' 1 / rc); every other gfx950
   // stencil entry refuses it with an Error.  Not part of form().
   const void* cap = nullptr;
   // the one place that reads src, wall and wall_beta for the form of the call
@@ -275,6 +278,19 @@ bool cond_sweep_supported(DType t, const KernelSpec& k, bool with_source);
 // deepest tv depth built for dtype t in the given form, every shallower depth
 // down to 2 being built in it too (0: none)
 int cond_sweep_max_depth(DType t, SweepForm form = {});
+// K-step sweep with a conductivity field and a heat capacity (stencil_tbc.hip;
+// spec tcK): the tv sweep whose every stage ends in cap_update.  Needs p.cond
+// and p.cap (without either: an Error naming the family that runs the call),
+// honours p.src and p.wall / p.wall_beta (stencil_tbc_wall.hip,
+// stencil_tbc_conv.hip); a form that is not built is an Error naming it, and
+// nothing is written; no fused check, no schedule tuning
+void stencil_cap_sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
+// Is the tc kernel of k's depth built for dtype t in the given form?  *shape,
+// if given, receives the tile (R rows x WY waves) that runs it.  No device access.
+bool cap_sweep_supported(DType t, const KernelSpec& k, SweepForm form = {}, LeanShape* shape = nullptr);
+// deepest tc depth built for dtype t in the given form, every shallower depth
+// down to 2 being built in it too (0: none)
+int cap_sweep_max_depth(DType t, SweepForm form = {});
 // Any multi-step kind -> its kernel
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream);
 void pack_box(DType t, const void* f, const Layout& L, const Box& b, void* buf, void* stream);
@@ -487,6 +503,16 @@ H3D_HD inline Real steady_increment_var(Real c, Real xm, Real xp, Real ym, Real 
   const Real fx = var_flux<Real>(c, xm, xp, hc + hxm, hc + hxp);
   const Real fy = var_flux<Real>(c, ym, yp, hc + hym, hc + hyp);
   const Real fz = var_flux<Real>(c, zm, zp, hc + hzm, hc + hzp);
+  return h3d_fma(Dz, fz, h3d_fma(Dy, fy, Dx * fx));
+}
+// ... from the six face weights (the sweep kernels form each weight where it is
+// used; the same operations in the same order)
+template <typename Real>
+H3D_HD inline Real steady_increment_varw(Real c, Real xm, Real xp, Real ym, Real yp, Real zm, Real zp, Real wxm,
+                                         Real wxp, Real wym, Real wyp, Real wzm, Real wzp, Real Dx, Real Dy, Real Dz) {
+  const Real fx = var_flux<Real>(c, xm, xp, wxm, wxp);
+  const Real fy = var_flux<Real>(c, ym, yp, wym, wyp);
+  const Real fz = var_flux<Real>(c, zm, zp, wzm, wzp);
   return h3d_fma(Dz, fz, h3d_fma(Dy, fy, Dx * fx));
 }
 // One step with a heat capacity, rc T_t = div(alpha c grad T) + q: the

@@ -129,8 +129,9 @@ void stencil_lean(DType t, const StencilParams& p, const KernelSpec& k, void* st
 }
 
 void sweep(DType t, const StencilParams& p, const KernelSpec& k, void* stream) {
-  HEAT3D_CHECK(k.multi_step(), "sweep needs a K-step kernel (tl2..tl6, tv2..tv3)");
+  HEAT3D_CHECK(k.multi_step(), "sweep needs a K-step kernel (tl2..tl6, tv2..tv3, tc2..tc3)");
   if (k.kind == KernelSpec::TBV) stencil_cond_sweep(t, p, k, stream);
+  else if (k.kind == KernelSpec::TBC) stencil_cap_sweep(t, p, k, stream);
   else stencil_lean(t, p, k, stream);
 }
 

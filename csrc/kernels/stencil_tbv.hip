@@ -109,8 +109,8 @@ void stencil_cond_sweep(DType t, const StencilParams& p, const KernelSpec& k, vo
   HEAT3D_CHECK(k.kind == KernelSpec::TBV, "stencil_cond_sweep needs a tv kernel");
   if (!p.cond) HEAT3D_THROW("tv kernels need a conductivity field (" << k.str() << " without one; use tl2..tl6)");
   if (p.cap)
-    HEAT3D_THROW("tv kernel " << k.str() << " has no heat-capacity form: with a capacity field every iteration runs "
-                                            "as a single step (tile | naive)");
+    HEAT3D_THROW("tv kernel " << k.str() << " has no heat-capacity form: with a capacity field use tc2 / tc3 (the tv "
+                                            "sweep with a capacity), or single steps (tile | naive)");
   HEAT3D_CHECK(!p.fuse_check && !p.tune, "tv kernels have no fused check and no schedule tuning");
   if (p.box.empty()) return;
   const SweepForm form = p.form();

@@ -23,6 +23,7 @@ constexpr int tbv_ahead(int K) { return K <= 3 ? 2 : 1; }
 
 // Textual inclusion, as the lean kernel's forms: the kernels without walls keep
 // the code and the names they had before the wall forms existed.
+#define H3D_TBV_CAP 0
 #define H3D_TBV_NAME stencil_tbv
 #define H3D_TBV_WALL 0
 #include "stencil_tbv_kernel.inc"
@@ -38,24 +39,54 @@ constexpr int tbv_ahead(int K) { return K <= 3 ? 2 : 1; }
 #include "stencil_tbv_kernel.inc"
 #undef H3D_TBV_NAME
 #undef H3D_TBV_WALL
+#undef H3D_TBV_CAP
+// ... and the tc kernels: the same three forms with a heat capacity
+// (H3D_TBV_CAP 1), instantiated in stencil_tbc.hip, stencil_tbc_wall.hip and
+// stencil_tbc_conv.hip
+#define H3D_TBV_CAP 1
+#define H3D_TBV_NAME stencil_tbc
+#define H3D_TBV_WALL 0
+#include "stencil_tbv_kernel.inc"
+#undef H3D_TBV_NAME
+#undef H3D_TBV_WALL
+#define H3D_TBV_NAME stencil_tbc_wall
+#define H3D_TBV_WALL 1
+#include "stencil_tbv_kernel.inc"
+#undef H3D_TBV_NAME
+#undef H3D_TBV_WALL
+#define H3D_TBV_NAME stencil_tbc_conv
+#define H3D_TBV_WALL 2
+#include "stencil_tbv_kernel.inc"
+#undef H3D_TBV_NAME
+#undef H3D_TBV_WALL
+#undef H3D_TBV_CAP
 
-// the kernel of wall form WALL (only the form that is asked for gets instantiated)
-template <typename Real, int R, int WY, int K, bool SRC, int WALL>
+// the kernel of wall form WALL, CAP: its heat-capacity form (only the form that
+// is asked for gets instantiated)
+template <typename Real, int R, int WY, int K, bool SRC, int WALL, bool CAP>
 constexpr auto tbv_kernel() {
-  if constexpr (WALL == 2) return &stencil_tbv_conv<Real, R, WY, K, SRC>;
-  else if constexpr (WALL == 1) return &stencil_tbv_wall<Real, R, WY, K, SRC>;
-  else return &stencil_tbv<Real, R, WY, K, SRC>;
+  if constexpr (CAP) {
+    if constexpr (WALL == 2) return &stencil_tbc_conv<Real, R, WY, K, SRC>;
+    else if constexpr (WALL == 1) return &stencil_tbc_wall<Real, R, WY, K, SRC>;
+    else return &stencil_tbc<Real, R, WY, K, SRC>;
+  } else {
+    if constexpr (WALL == 2) return &stencil_tbv_conv<Real, R, WY, K, SRC>;
+    else if constexpr (WALL == 1) return &stencil_tbv_wall<Real, R, WY, K, SRC>;
+    else return &stencil_tbv<Real, R, WY, K, SRC>;
+  }
 }
 
 // WALL: 0 no walls, 1 the insulated-wall form (p.wall), 2 the convective-wall
-// form (p.wall_beta, p.ambient as well), as StencilParams::form() names them
-template <typename Real, int R, int WY, int K, bool SRC, int WALL = 0>
+// form (p.wall_beta, p.ambient as well), as StencilParams::form() names them.
+// CAP: the tc kernels (p.cap as well; the callers have checked that it is set).
+template <typename Real, int R, int WY, int K, bool SRC, int WALL = 0, bool CAP = false>
 static void launch_tbv(const StencilParams& p, const KernelSpec& ks, hipStream_t s) {
-  constexpr auto kernel = tbv_kernel<Real, R, WY, K, SRC, WALL>();
+  constexpr auto kernel = tbv_kernel<Real, R, WY, K, SRC, WALL, CAP>();
   const void* kfn = reinterpret_cast<const void*>(kernel);
   const SweepForm form = p.form();
   HEAT3D_CHECK(SRC == form.src, "tv: source form mismatch");
   HEAT3D_CHECK(WALL == (int)form.wall, "tv: wall form mismatch");
+  HEAT3D_CHECK(CAP == (p.cap != nullptr) && p.cond, "tv: conductivity / capacity form mismatch");
   const Box& b = p.box;
   const Layout& L = p.L;
   constexpr int TY = WY * R;
@@ -129,8 +160,17 @@ static void launch_tbv(const StencilParams& p, const KernelSpec& ks, hipStream_t
   const Real* src = static_cast<const Real*>(p.src);
   const Real Dx = (Real)p.D[0], Dy = (Real)p.D[1], Dz = (Real)p.D[2];
   const dim3 grid((unsigned)nblocks), block(64 * WY);
+  // (the wall forms' arguments sit between g and Dx; the tc kernels take s after the source)
+  auto launch = [&](auto... wall_args) {
+    if constexpr (CAP) {
+      const Real* cap = static_cast<const Real*>(p.cap);
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, in, out, ch, src, cap, g, wall_args..., Dx, Dy, Dz, r, done);
+    } else {
+      hipLaunchKernelGGL(kernel, grid, block, 0, s, in, out, ch, src, g, wall_args..., Dx, Dy, Dz, r, done);
+    }
+  };
   if constexpr (WALL == 0) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, s, in, out, ch, src, g, Dx, Dy, Dz, r, done);
+    launch();
   } else {
     // the walls in the kernel's frame (as launch_tbl; the tv kernels have no swapped form)
     TBLWalls wl{};
@@ -144,7 +184,7 @@ static void launch_tbv(const StencilParams& p, const KernelSpec& ks, hipStream_t
       wl.z[e] = coord(p.wall[2][e], e);
     }
     if constexpr (WALL == 1) {
-      hipLaunchKernelGGL(kernel, grid, block, 0, s, in, out, ch, src, g, wl, Dx, Dy, Dz, r, done);
+      launch(wl);
     } else {
       // ... and the convective coefficients (an insulated face: 0)
       TBLConv<Real> cv{};
@@ -157,7 +197,7 @@ static void launch_tbv(const StencilParams& p, const KernelSpec& ks, hipStream_t
         cv.z[e] = beta(2, e);
       }
       cv.tinf = (Real)p.ambient;
-      hipLaunchKernelGGL(kernel, grid, block, 0, s, in, out, ch, src, g, wl, cv, Dx, Dy, Dz, r, done);
+      launch(wl, cv);
     }
   }
   HIPK_CHECK(hipGetLastError());
@@ -177,6 +217,20 @@ bool tbv_conv_dispatch(DType t, bool src, const StencilParams* p, const KernelSp
     if (shape) *shape = LeanShape{RR, YY, false};                \
     if (p) launch_tbv<Real, RR, YY, KK, SRCB, WALL>(*p, k, s);   \
     return true;                                                 \
+  }
+
+// The tc kernels' dispatch, one per translation unit (stencil_tbc.hip: no
+// walls, stencil_tbc_wall.hip, stencil_tbc_conv.hip), as the wall forms' above.
+bool tbc_plain_dispatch(DType t, bool src, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape);
+bool tbc_wall_dispatch(DType t, bool src, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape);
+bool tbc_conv_dispatch(DType t, bool src, const StencilParams* p, const KernelSpec& k, hipStream_t s, LeanShape* shape);
+
+// One line of a tc unit's shape list (as H3D_TBV_WALL_SHAPE)
+#define H3D_TBC_SHAPE(WALL, SRCB, KK, RR, YY)                          \
+  if (k.K == KK && src == SRCB) {                                      \
+    if (shape) *shape = LeanShape{RR, YY, false};                      \
+    if (p) launch_tbv<Real, RR, YY, KK, SRCB, WALL, true>(*p, k, s);   \
+    return true;                                                       \
   }
 
 }  // namespace hip

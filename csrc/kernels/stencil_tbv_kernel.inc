@@ -10,9 +10,20 @@
 // the form without walls: Ch is read at the wall vertex.  A wave, tile or plane
 // step that holds a wall-adjacent row, column or stage plane never takes the
 // mask-free step, which is the code of the form without walls.
+//
+// H3D_TBV_CAP 1: the tc kernels (stencil_tbc*.hip), the same sweep with a heat
+// capacity.  One more static field, s = dtype(1 / rc), of which a stage reads
+// the centre value of the point it updates, nothing else: it is loaded where it
+// is used, as the source rows are, and the update becomes kernels.hpp
+// cap_update on the step's increment (steady_increment_var's chain, started
+// from zero, then the source).  With H3D_TBV_CAP 0 the text is that of the tv
+// kernels.
 template <typename Real, int R, int WY, int K, bool SRC>
 __global__ __launch_bounds__(64 * WY) void H3D_TBV_NAME(const Real* __restrict__ in, Real* __restrict__ out,
                                                        const Real* __restrict__ ch, const Real* __restrict__ src,
+#if H3D_TBV_CAP
+                                                       const Real* __restrict__ cap,
+#endif
                                                        TBLArgs g,
 #if H3D_TBV_WALL
                                                        TBLWalls wa,
@@ -144,6 +155,12 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBV_NAME(const Real* __restrict__
   const Real* __restrict__ chw = ch + (g.origin + (int64_t)ybm * g.sy + c0);
   Real* __restrict__ outw = out + (g.origin + (int64_t)yb * g.sy + c0);
   const Real* __restrict__ srcw = SRC ? src + (g.origin + (int64_t)ybc * g.sy + c0) : nullptr;
+#if H3D_TBV_CAP
+  // the capacity field has the field's layout (StencilParams::cap: L.bytes()),
+  // and it is read at T's own clamped plane, row and lane offsets: every offset
+  // that is in bounds for T is in bounds for s
+  const Real* __restrict__ capw = cap + (g.origin + (int64_t)ybc * g.sy + c0);
+#endif
   int roff[R], coff[R + 2];
 #pragma unroll
   for (int r = 0; r < R; ++r) roff[r] = sgpr((yclamp(yb + r) - ybc) * (int)g.sy * (int)sizeof(Real));
@@ -219,6 +236,17 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBV_NAME(const Real* __restrict__
 #pragma unroll
         for (int r = 0; r < R; ++r) S[r] = buf_load<Real>(rs, lane_b, roff[r]);
       }
+#if H3D_TBV_CAP
+      // s on this stage's plane, the wave's own rows, the lane's own column (it
+      // has no neighbours: no ring).  A clamped plane or row only ever feeds a
+      // masked-out result, as T's, Ch's and S's do.
+      Real A[R];
+      {
+        const __amdgpu_buffer_rsrc_t rs = plane_rsrc(capw + (int64_t)xclamp(p) * sx);
+#pragma unroll
+        for (int r = 0; r < R; ++r) A[r] = buf_load<Real>(rs, lane_b, roff[r]);
+      }
+#endif
       // masked form: uniform x conditions of this stage
       bool xin = true, xcnt = true, xst = true;
       if constexpr (!FAST) {
@@ -271,8 +299,15 @@ __global__ __launch_bounds__(64 * WY) void H3D_TBV_NAME(const Real* __restrict__
         const Real wxm = hc + HM[r + 1], wxp = hc + HP[r + 1];
         const Real wym = hc + HC[r], wyp = hc + HC[r + 2];
         const Real wzm = hc + dpp_shr1z(hc), wzp = hc + dpp_shl1z(hc);
+#if H3D_TBV_CAP
+        // the increment of the step, then the source, then T' = fma(s, u, T)
+        Real u = steady_increment_varw<Real>(C[r], xm, xp, ym, yp, zm, zp, wxm, wxp, wym, wyp, wzm, wzp, Dx, Dy, Dz);
+        if constexpr (SRC) u = add_source<Real>(u, S[r]);
+        const Real nv = cap_update<Real>(A[r], u, C[r]);
+#else
         Real nv = ftcs_update_varw<Real>(C[r], xm, xp, ym, yp, zm, zp, wxm, wxp, wym, wyp, wzm, wzp, Dx, Dy, Dz);
         if constexpr (SRC) nv = add_source<Real>(nv, S[r]);
+#endif
         const Real d = resid_abs_r(nv, C[r]);
         bool upd = true, cnt = true, st = true;
         if constexpr (!FAST) {

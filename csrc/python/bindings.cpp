@@ -375,6 +375,24 @@ PYBIND11_MODULE(_heat3d, m) {
     if (wall < 0 || wall > 2) throw UsageError("cond_sweep_max_depth: wall is 0 (none), 1 (insulated) or 2 (convective)");
     return heat3d::hip::cond_sweep_max_depth(dt_of(dtype), SweepForm{with_source, static_cast<WallKind>(wall)});
   }, py::arg("dtype"), py::arg("with_source") = false, py::arg("wall") = 0);
+  // the same three queries for the tc sweep (conductivity and heat capacity; spec tc2 / tc3)
+  m.def("cap_sweep_supported", [](const std::string& dtype, const std::string& spec, bool with_source, int wall) {
+    if (wall < 0 || wall > 2) throw UsageError("cap_sweep_supported: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    return heat3d::hip::cap_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec),
+                                            SweepForm{with_source, static_cast<WallKind>(wall)});
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false, py::arg("wall") = 0);
+  m.def("cap_sweep_shape", [](const std::string& dtype, const std::string& spec, bool with_source, int wall) -> py::object {
+    if (wall < 0 || wall > 2) throw UsageError("cap_sweep_shape: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    heat3d::hip::LeanShape sh;
+    if (!heat3d::hip::cap_sweep_supported(dt_of(dtype), heat3d::KernelSpec::parse(spec),
+                                          SweepForm{with_source, static_cast<WallKind>(wall)}, &sh))
+      return py::none();
+    return py::make_tuple(sh.R, sh.WY);
+  }, py::arg("dtype"), py::arg("spec"), py::arg("with_source") = false, py::arg("wall") = 0);
+  m.def("cap_sweep_max_depth", [](const std::string& dtype, bool with_source, int wall) {
+    if (wall < 0 || wall > 2) throw UsageError("cap_sweep_max_depth: wall is 0 (none), 1 (insulated) or 2 (convective)");
+    return heat3d::hip::cap_sweep_max_depth(dt_of(dtype), SweepForm{with_source, static_cast<WallKind>(wall)});
+  }, py::arg("dtype"), py::arg("with_source") = false, py::arg("wall") = 0);
   m.def("rccl_unique_id", []() { return py::bytes(rccl_unique_id()); });
   m.def("rccl_version", &rccl_version);
   // the HIP runtime / RCCL this process is bound to (bench JSON "runtime")

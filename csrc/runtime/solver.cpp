@@ -80,10 +80,11 @@ KernelSpec KernelSpec::parse(const std::string& s) {
     if (k.kind != Tile && parts.size() > 8) k.ZS = at(8);  // z tile stride
     if (k.kind != Tile && parts.size() > 9) k.EW = at(9);  // edge role (1 + owned rows of the halo waves)
     if (k.EW < 0) throw UsageError("kernel '" + s + "': the edge-role field is 0 (off) or 1 + rows");
-  } else if (h.size() == 3 && h[0] == 't' && h[1] == 'v' && h[2] >= '2' && h[2] <= '4') {
+  } else if (h.size() == 3 && h[0] == 't' && (h[1] == 'v' || h[1] == 'c') && h[2] >= '2' && h[2] <= '4') {
     // tv2..tv4 = K-step sweep with a conductivity field; one shape per depth,
     // only the schedule fields (x segment length, z tile stride) are read
-    k.kind = TBV;
+    // tc2..tc4 = the same with a heat capacity as well
+    k.kind = h[1] == 'c' ? TBC : TBV;
     k.K = h[2] - '0';
     auto at = [&](std::size_t i) { return parts.size() > i ? std::atoi(parts[i].c_str()) : 0; };
     k.V = at(1);
@@ -99,7 +100,7 @@ KernelSpec KernelSpec::parse(const std::string& s) {
                      "use tile for single steps and tl2..tl6 for K-step sweeps");
   } else {
     throw UsageError("unknown kernel '" + s + "' (auto | naive | tile[:V[:R[:WZ[:WY]]]] | "
-                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS[:EDGE]]]]]]]]] | tv2..tv3)");
+                     "tl2..tl6[:V[:R[:WZ[:WY[:L[:Q[:STORE[:ZS[:EDGE]]]]]]]]] | tv2..tv3 | tc2..tc3)");
   }
   return k;
 }
@@ -186,7 +187,7 @@ KernelSpec KernelSpec::resolved(DType t) const {
 std::string KernelSpec::str() const {
   if (kind == Naive) return "naive";
   std::ostringstream os;
-  os << (kind == Tile ? std::string("tile:") : (kind == TBV ? "tv" : "tl") + std::to_string(K) + ":") << V << ":" << R << ":" << WZ << ":"
+  os << (kind == Tile ? std::string("tile:") : (kind == TBV ? "tv" : kind == TBC ? "tc" : "tl") + std::to_string(K) + ":") << V << ":" << R << ":" << WZ << ":"
      << WY << ":" << L << ":" << NT;
   if (kind != Tile && (O > 0 || ZS > 0 || EW > 0)) os << ":" << O;
   if (kind != Tile && (ZS > 0 || EW > 0)) os << ":" << ZS;
@@ -229,8 +230,9 @@ Solver::Solver(const Config& cfg, std::unique_ptr<Backend> be, std::unique_ptr<C
   kspec_ = KernelSpec::parse(cfg_.kernel);
   if (kspec_.multi_step()) kspec_.kind = KernelSpec::Tile;
   kspec2_ = KernelSpec::parse(cfg_.kernel2);
-  // (the tv family is chosen by --conductivity-sweeps, not by --kernel2: it only gives the depth)
-  if (kspec2_.kind == KernelSpec::TBV) {
+  // (the tv / tc families are chosen by --conductivity-sweeps / --capacity-sweeps, not by --kernel2: it
+  // only gives the depth)
+  if (kspec2_.kind == KernelSpec::TBV || kspec2_.kind == KernelSpec::TBC) {
     const int k2 = kspec2_.K;
     kspec2_ = KernelSpec{};
     kspec2_.kind = KernelSpec::TBL;
@@ -559,7 +561,10 @@ void Solver::preflight_extra_field(const char* what, std::size_t extra) {
 bool Solver::lean_ok(const KernelSpec& ks) const { return hip::lean_supported(dt_, ks, sweep_form()); }
 
 void Solver::set_cond_depth() {
-  Kc_ = !tb_ ? 0 : be_->is_gpu() ? std::min(K_, hip::cond_sweep_max_depth(dt_, sweep_form())) : K_;
+  const auto deepest = [&] {
+    return has_cap_ ? hip::cap_sweep_max_depth(dt_, sweep_form()) : hip::cond_sweep_max_depth(dt_, sweep_form());
+  };
+  Kc_ = !tb_ ? 0 : be_->is_gpu() ? std::min(K_, deepest()) : K_;
 }
 
 void Solver::set_walls(StencilParams& sp, const Local& l) const {
@@ -730,7 +735,8 @@ void Solver::retune() {
   rl_ = false;
   for (bool& b : rl_d_) b = false;
   // a conductivity field: single steps, or the tv sweeps (one shape per
-  // depth, every residual): nothing to time; nor with a heat capacity
+  // depth, every residual): nothing to time; nor with a heat capacity (single
+  // steps or the tc sweeps)
   if (has_cond_ || has_cap_ || walls_single()) return;
   tune_schedules();
   calibrate_remainders();
@@ -1013,7 +1019,7 @@ void Solver::tune_schedules() {
 KernelSpec Solver::spec_for_depth(int Kp) const {
   if (cond_sweeping()) {
     KernelSpec kv;
-    kv.kind = KernelSpec::TBV;
+    kv.kind = has_cap_ ? KernelSpec::TBC : KernelSpec::TBV;
     kv.K = Kp;
     return kv;
   }
@@ -1526,8 +1532,9 @@ void Solver::enqueue_multi(int bi, int Kp, bool thick) {
   const bool lb = dv || (thick && long_halo_);
   H3D_TRACE("sweep" << Kp << " issued=" << issued_ << " buf=" << bi << (capturing_ ? " (capturing)" : ""));
   HEAT3D_CHECK(tb_, "temporal blocking not enabled for this decomposition");
-  HEAT3D_CHECK(!has_cond_ || (cond_sweeping() && Kp <= Kc_),
-               "K-step sweeps have no conductivity form (--conductivity-sweeps: tv sweeps up to depth " << Kc_ << ")");
+  HEAT3D_CHECK(!(has_cond_ || has_cap_) || (cond_sweeping() && Kp <= Kc_),
+               "K-step sweeps have no conductivity / heat-capacity form (--conductivity-sweeps: tv sweeps, with a "
+               "capacity --capacity-sweeps: tc sweeps, up to depth " << Kc_ << ")");
   if (last_kind_ != 2) join_pipeline();
   last_kind_ = 2;
   // lagged schedule: events and residual slots alternate by sweep parity

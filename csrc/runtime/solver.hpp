@@ -193,14 +193,20 @@ class Solver {
   // updated point is read).  While a capacity is set every iteration runs as a
   // single step (kernels.hpp cap_update; with walls on refreshed wall planes):
   // no K-step sweeps, no fused check, no long sweeps, no start-up timing;
-  // Config::cond_sweeps and Config::wall_source_sweeps mean nothing.  Setting
-  // or clearing behaves like set_conductivity.  Not with --compat.
+  // Config::cond_sweeps and Config::wall_source_sweeps mean nothing.  With a
+  // conductivity set as well, Config::cap_sweeps asks for the K-step sweeps of
+  // the tc kernel family (stencil_tbc.hip; depth min(K, the deepest tc kernel
+  // built in the run's form), scheduled exactly as the tv sweeps are); without
+  // a conductivity that flag does nothing (the uniform step's increment is
+  // steady_increment, which no sweep kernel computes).  Setting or clearing
+  // behaves like set_conductivity.  Not with --compat.
   void set_capacity(const double* global_rc);
   void set_capacity_file(const std::string& path);
   void clear_capacity();
   bool has_capacity() const { return has_cap_; }
   // K-step sweeps are what run() / step() issue (temporal blocking on, and no
-  // conductivity field or Config::cond_sweeps)
+  // conductivity field or Config::cond_sweeps; with a heat capacity: a
+  // conductivity field and Config::cap_sweeps)
   bool sweeps_active() const { return sweeping(); }
   // ... in the overlapped schedule (interior on the compute stream, deep halo
   // and boundary pieces on the comm stream; sweep_pieces lists the pieces)
@@ -376,12 +382,16 @@ class Solver {
   void preflight_source();
   bool has_cond_ = false;
   bool has_cap_ = false;
-  // K-step sweeps run (temporal blocking on, no heat capacity, and no
-  // conductivity field or the tv sweeps asked for)
-  bool sweeping() const { return tb_ && !has_cap_ && (!has_cond_ || cond_sweeping()) && !walls_single(); }
-  // ... of the tv family, with the conductivity field (--conductivity-sweeps)
-  // (behind walls too: the wall forms of the tv kernels)
-  bool cond_sweeping() const { return tb_ && has_cond_ && !has_cap_ && cfg_.cond_sweeps && Kc_ >= 2; }
+  // K-step sweeps run (temporal blocking on, and no conductivity field and no
+  // heat capacity, or the tv / tc sweeps asked for)
+  bool sweeping() const { return tb_ && ((!has_cond_ && !has_cap_) || cond_sweeping()) && !walls_single(); }
+  // ... of the tv family, with the conductivity field (--conductivity-sweeps),
+  // or, with a heat capacity as well, of the tc family (--capacity-sweeps, which
+  // alone decides while a capacity is set)
+  // (behind walls too: the wall forms of the tv / tc kernels)
+  bool cond_sweeping() const {
+    return tb_ && has_cond_ && (has_cap_ ? cfg_.cap_sweeps : cfg_.cond_sweeps) && Kc_ >= 2;
+  }
   // Insulated walls (Config::insulated).  Sweeps run the wall forms of the
   // lean kernel (StencilParams::wall: the substitution happens in the kernel,
   // at every stage).  Single steps run the kernels as they are on wall planes
@@ -402,8 +412,8 @@ class Solver {
   unsigned walls_ = 0, conv_ = 0;
   double conv_beta_[6] = {-1, -1, -1, -1, -1, -1};
   bool walls_single() const {
-    // (a heat capacity: single steps whatever else is set)
-    return walls_ && (has_cap_ || (has_cond_ ? !cond_sweeping() : has_source_ && !cfg_.wall_source_sweeps));
+    // (a heat capacity: single steps whatever else is set, but for the tc sweeps)
+    return walls_ && (has_cond_ || has_cap_ ? !cond_sweeping() : has_source_ && !cfg_.wall_source_sweeps);
   }
   // the form of this run's sweeps: a source or not, behind which kind of wall
   SweepForm sweep_form() const {
@@ -418,11 +428,12 @@ class Solver {
   void refresh_walls(int b, StreamId s);
   // is the lean variant built in the form this run needs (source / walls)?
   bool lean_ok(const KernelSpec& ks) const;
-  // steps per sweep of the schedule: K_, or the tv sweeps' depth Kc_ <= K_ (a
+  // steps per sweep of the schedule: K_, or the tv / tc sweeps' depth Kc_ <= K_ (a
   // sweep shallower than the ghost depth K_ is what a partial sweep is)
   int sweep_depth() const { return cond_sweeping() ? Kc_ : K_; }
-  // min(K_, deepest tv depth built for the dtype in the run's form); the CPU
-  // backend: K_.  Set again wherever the form changes (a source set or cleared).
+  // min(K_, deepest tv depth built for the dtype in the run's form; with a heat
+  // capacity: deepest tc depth); the CPU backend: K_.  Set again wherever the
+  // form changes (a source or a capacity set or cleared).
   int Kc_ = 0;
   void set_cond_depth();
   void preflight_extra_field(const char* what, std::size_t extra);

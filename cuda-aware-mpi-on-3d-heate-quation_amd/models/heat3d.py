@@ -274,7 +274,8 @@ class HeatSolver:
                  check_every: int = 64, graph_chunk: int = 0, device: Optional[int] = None,
                  threads: int = 0, extra_args: Sequence[str] = (), group=None,
                  phantom: Optional[Sequence[int]] = None, conductivity_sweeps: bool = False,
-                 insulated=None, convective=None, ambient: float = 0.0, wall_source_sweeps: bool = False):
+                 insulated=None, convective=None, ambient: float = 0.0, wall_source_sweeps: bool = False,
+                 capacity_sweeps: bool = False):
         ext = native()
         self.model = HeatEquation3D(tuple(int(v) for v in n))  # type: ignore[arg-type]
         args: List[str] = [str(int(v)) for v in n] + [str(int(iter_max)), _fmt(eps)]
@@ -295,6 +296,9 @@ class HeatSolver:
         if conductivity_sweeps:
             # with a conductivity field: K-step sweeps of the tv kernels instead of single steps
             args.append("--conductivity-sweeps")
+        if capacity_sweeps:
+            # with a heat capacity and a conductivity field: K-step sweeps of the tc kernels instead of single steps
+            args.append("--capacity-sweeps")
         if wall_source_sweeps:
             # with insulated / convective walls and a heat source: K-step sweeps instead of single steps
             args.append("--wall-source-sweeps")
@@ -438,8 +442,10 @@ class HeatSolver:
         the time step stays stable).  A value below 1 or not finite is the native
         ``UsageError`` (a RuntimeError) naming the first offending index, raised
         on every rank.  While set, every iteration runs as a single step
-        (``conductivity_sweeps`` and ``wall_source_sweeps`` mean nothing), the
-        stored heat of ``heat_balance()`` is weighted with rc, and the steady
+        (``conductivity_sweeps`` and ``wall_source_sweeps`` mean nothing) unless a
+        conductivity is set too and ``capacity_sweeps=True`` asks for the K-step
+        sweeps of the tc kernels (same bits; without a conductivity that flag
+        does nothing), the stored heat of ``heat_balance()`` is weighted with rc, and the steady
         state (``solve_steady``) is the one without a capacity.  A body with
         rc == 1 everywhere agrees with one without a capacity to rounding, not
         bitwise.  Keeps the field, restarts the iteration count and the

@@ -262,7 +262,9 @@ def sweep(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Sequence[
     and a tv kernel needs one: RuntimeError either way), CPU tensors run the
     K-single-steps definition with it.  ``cap``: the heat-capacity field
     s = dtype(1 / rc) in the same layout: CPU tensors run K single steps with it
-    (the definition); no gfx950 sweep kernel has a capacity form (RuntimeError)."""
+    (the definition); on the GPU it needs ``conductivity`` as well and a ``tc2`` /
+    ``tc3`` kernel (stencil_tbc.hip), with real 1 / rc values on every ghost layer
+    the update ranges reach; any other sweep kernel refuses it (RuntimeError)."""
     if src.layout != dst.layout or src.dtype != dst.dtype or src.device != dst.device:
         raise ValueError("src and dst must share layout, dtype and device")
     sptr = 0
