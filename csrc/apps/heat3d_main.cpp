@@ -113,6 +113,8 @@ static int drive(const Config& cfg, Solver& solver) {
   if (!cfg.initial_file.empty()) solver.set_field_file(cfg.initial_file);
   RunResult r;
   SteadyResult sr;
+  ImplicitResult ir;
+  static const char* kCgStatus[] = {"running", "converged", "max_iter", "breakdown"};
   if (cfg.steady_solve) {
     // EPS is the relative tolerance, ITER_MAX caps the CG iterations (collective)
     try {
@@ -125,6 +127,18 @@ static int drive(const Config& cfg, Solver& solver) {
       return 1;
     }
     r.seconds = sr.seconds;
+  } else if (cfg.implicit) {
+    // ITER_MAX implicit steps of M explicit steps each, EPS the CG tolerance (collective)
+    try {
+      ir = solver.step_implicit(cfg.iter_max, cfg.implicit_m, cfg.implicit_theta, cfg.eps);
+    } catch (const UsageError& e) {
+      if (root) {
+        std::cout << Config::usage() << std::flush;
+        std::cerr << "heat3d: " << e.what() << std::endl;
+      }
+      return 1;
+    }
+    r.seconds = ir.seconds;
   } else {
     r = solver.run();
   }
@@ -142,13 +156,21 @@ static int drive(const Config& cfg, Solver& solver) {
       std::printf("heat3d: steady solve: status=%s restarts=%d residual=%.6e true_residual=%.6e r0_norm=%.6e\n",
                   kStatus[sr.status >= 0 && sr.status < 4 ? sr.status : 0], sr.restarts, sr.residual,
                   sr.true_residual, sr.r0_norm);
+    } else if (cfg.implicit) {
+      std::printf("Implicit steps (theta = %g, conjugate gradients): %lld of %lld steps of %g explicit steps each, "
+                  "%lld iterations, every step %s the relative tolerance of %e\n",
+                  cfg.implicit_theta, (long long)ir.steps_done, (long long)cfg.iter_max, cfg.implicit_m,
+                  (long long)ir.iterations, ir.converged ? "within" : "NOT within", cfg.eps);
+      std::printf("heat3d: implicit: status=%s restarts=%d residual=%.6e true_residual=%.6e r0_norm=%.6e\n",
+                  kCgStatus[ir.status >= 0 && ir.status < 4 ? ir.status : 0], ir.restarts, ir.residual,
+                  ir.true_residual, ir.r0_norm);
     } else if (r.converged)
       std::printf("Simulation has converged in %lld iterations with a convergence threshold of %e\n",
                   (long long)r.conv_iter, cfg.eps);
     else
       std::printf("Simulation did not converge within %lld iterations.\n", (long long)cfg.iter_max);
     std::printf("L2-norm error: %.4f %%\n", 100.0 * (cfg.compat ? lerr : gerr));
-    if (!cfg.compat && !cfg.steady_solve) {
+    if (!cfg.compat && !cfg.steady_solve && !cfg.implicit) {
       const auto& d = solver.decomposition();
       std::printf("heat3d: backend=%s comm=%s ranks=%d dims=%dx%dx%d dtype=%s kernel=%s "
                   "iterations=%lld issued=%lld GLUPS=%.3f eff_TBps=%.3f norm=%.6e last_residual=%.6e\n",
@@ -235,6 +257,28 @@ static int drive(const Config& cfg, Solver& solver) {
       s.set("status", std::string(kStatus[sr.status >= 0 && sr.status < 4 ? sr.status : 0]));
       s.set("tol", cfg.eps);
       j.set_raw("steady_solve", s.dump());
+    }
+    if (cfg.implicit) {
+      io::Json s;
+      std::string its = "[";
+      for (std::size_t i = 0; i < ir.step_iterations.size(); ++i)
+        its += (i ? ", " : "") + std::to_string(ir.step_iterations[i]);
+      s.set_bool("converged", ir.converged);
+      s.set("steps", (int64_t)cfg.iter_max);
+      s.set("steps_done", (int64_t)ir.steps_done);
+      s.set("m", cfg.implicit_m);
+      s.set("theta", cfg.implicit_theta);
+      s.set("time_advanced", ir.time_advanced);
+      s.set("iterations", (int64_t)ir.iterations);
+      s.set_raw("step_iterations", its + "]");
+      s.set("residual", ir.residual);
+      s.set("true_residual", ir.true_residual);
+      s.set("r0_norm", ir.r0_norm);
+      s.set("seconds", ir.seconds);
+      s.set("restarts", (int64_t)ir.restarts);
+      s.set("status", std::string(kCgStatus[ir.status >= 0 && ir.status < 4 ? ir.status : 0]));
+      s.set("tol", cfg.eps);
+      j.set_raw("implicit", s.dump());
     }
     if (cfg.heat_balance) {
       io::Json b, fl;

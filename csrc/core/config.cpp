@@ -222,6 +222,11 @@ std::string Config::usage() {
      << "                            of the residual's 2-norm, ITER_MAX caps the iterations; a \"steady_solve\"\n"
      << "                            object in --json-out (fp64 only; not with --compat; needs a Dirichlet face or\n"
      << "                            a convective face with a positive coefficient)\n"
+     << "  --implicit M[:THETA]      implicit time steps instead of the explicit time loop: ITER_MAX steps of M\n"
+     << "                            explicit time steps each (THETA 1: backward Euler, the default; 0.5: Crank-\n"
+     << "                            Nicolson), each solved by conjugate gradients on the device to the relative\n"
+     << "                            tolerance EPS; honours --capacity; an \"implicit\" object in --json-out (fp64\n"
+     << "                            only; not with --compat or --steady-solve)\n"
      << "  --initial FILE            initial field, same format: its boundary vertices are the fixed wall\n"
      << "                            values, its interior T^0 (the error report still measures against T = y)\n"
      << "  --json-out PATH           write a JSON run report\n"
@@ -374,6 +379,13 @@ Config Config::parse(int argc, const char* const* argv) {
     else if (key == "--wall-source-sweeps") c.wall_source_sweeps = true;
     else if (key == "--heat-balance") c.heat_balance = true;
     else if (key == "--steady-solve") c.steady_solve = true;
+    else if (key == "--implicit") {
+      const std::string v = get("--implicit");
+      const auto colon = v.find(':');
+      c.implicit = true;
+      c.implicit_m = to_f64(v.substr(0, colon), "--implicit");
+      c.implicit_theta = colon == std::string::npos ? 1.0 : to_f64(v.substr(colon + 1), "--implicit");
+    }
     else if (key == "--insulated") c.insulated = parse_insulated(get("--insulated"));
     else if (key == "--convective") c.convective = parse_convective(get("--convective"));
     else if (key == "--ambient") {
@@ -531,6 +543,19 @@ Config Config::parse(int argc, const char* const* argv) {
     if (!anchored)
       throw UsageError("--steady-solve needs a Dirichlet face or a convective face with a positive coefficient: "
                        "with every face insulated the system is singular");
+  }
+  if (c.implicit) {
+    if (c.steady_solve) throw UsageError("--implicit and --steady-solve exclude each other");
+    if (c.compat || c.scheme == "reference")
+      throw UsageError("--implicit is not part of --compat / --scheme reference (the reference's explicit step)");
+    if (c.dtype != DType::F64)
+      throw UsageError("--implicit needs --dtype fp64: in fp32 conjugate gradients cannot get below about kappa * 2^-24");
+    if (!(c.implicit_m > 0.0) || !std::isfinite(c.implicit_m))
+      throw UsageError("--implicit: M, the step length in explicit time steps, must be positive and finite");
+    if (!(c.implicit_theta >= 0.5 && c.implicit_theta <= 1.0))
+      throw UsageError("--implicit: THETA must lie in [0.5, 1] (1: backward Euler, 0.5: Crank-Nicolson)");
+    if (!(c.eps > 0.0) || !std::isfinite(c.eps))
+      throw UsageError("--implicit: EPS is the relative tolerance of each step's solve and must be positive");
   }
   if (c.wall_source_sweeps && c.compat)
     throw UsageError("--wall-source-sweeps is not part of --compat (the reference has neither walls nor a source)");

@@ -86,6 +86,12 @@ struct Config {
   // initial field: EPS is the relative tolerance of the residual's 2-norm,
   // ITER_MAX caps the CG iterations; a "steady_solve" object in --json-out.
   bool steady_solve = false;
+  // --implicit M[:THETA]: instead of the time loop, Solver::step_implicit from
+  // the initial field: ITER_MAX implicit steps of M explicit time steps each
+  // (THETA in [0.5, 1], default 1), EPS the CG tolerance; an "implicit" object
+  // in --json-out.
+  bool implicit = false;
+  double implicit_m = 0.0, implicit_theta = 1.0;
   std::string conductivity_file;  // --conductivity: relative conductivity c in (0, 1], same format
   std::string capacity_file;  // --capacity: relative volumetric heat capacity rc >= 1, same format
   std::string initial_file;  // --initial: initial field with its wall values, same format

@@ -539,6 +539,16 @@ template <typename Real>
 H3D_HD inline Real steady_axpy(Real a, Real x, Real y) {
   return h3d_fma(a, x, y);
 }
+// The shifted operator of an implicit step at one point, (R + mu A) p with
+// R = diag(rc) stored as s = 1 / rc: `inc` is the increment of the homogeneous
+// step at p (steady_increment / steady_increment_var, so A p = -inc), one
+// correctly rounded division and one fused multiply-add.  Without a capacity
+// R = I and s is not read.
+template <bool CAP, typename Real>
+H3D_HD inline Real implicit_apply(Real qc, Real inc, Real mu, Real s) {
+  if constexpr (CAP) return h3d_fma(-mu, inc, qc / s);
+  else return h3d_fma(-mu, inc, qc);
+}
 
 // Residual term of one point, |T^{n+1} - T^n|, taken in the field's
 // precision as the reference takes fabs(T - T0) in its field type

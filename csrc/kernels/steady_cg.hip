@@ -10,9 +10,13 @@
 //       (steady_wall_neighbour), never multiplied away, so a wall vertex may
 //       hold anything.  Conductivity, residual form, source and "any wall in
 //       reach" are template arguments.  Every lane adds its float64 products
-//       p q (or r r) to one double-double accumulator.
+//       p q (or r r) to one double-double accumulator.  The shifted A-forms of
+//       an implicit step, q = (R + mu A) p (implicit_apply; with or without the
+//       capacity field), are one more template argument.
 //   steady_update_kernel  x += alpha p, r -= alpha q and r . r: a wave per z
-//       row, four pieces loaded ahead of the arithmetic.
+//       row, four pieces loaded ahead of the arithmetic.  Two more forms: r
+//       alone (r -= q, the true residual of an implicit step) and x alone
+//       (T' = fma(m, d, T)).
 //   steady_direction_kernel  p = r + beta p, the same shape.
 //   steady_final_kernel   one workgroup combines the per-workgroup partials in a
 //       fixed order (thread t takes t, t + 256, ...; then shuffles; then the
@@ -63,14 +67,19 @@ struct ApplyGeom {
   int64_t ntasks;
 };
 
-template <bool COND, bool RESID, bool SRC, bool WALLS>
+// SHIFT: 0 the plain forms, 1 the shifted A-form of an implicit step
+// (implicit_apply), 2 the same with a capacity: s is one more streamed load at
+// the centre of each updated point, issued where it is used
+template <bool COND, bool RESID, bool SRC, bool WALLS, int SHIFT = 0>
 __global__ __launch_bounds__(kCgThreads) void steady_apply_kernel(SteadyApplyParams p, ApplyGeom g, DD* partial) {
+  static_assert(!(RESID && SHIFT), "the residual form is not shifted");
   __shared__ DD red[kCgWaves];
   if (cg_done(p.state)) return;  // uniform across the grid
   const double* __restrict__ in = static_cast<const double*>(p.in);
   double* __restrict__ out = static_cast<double*>(p.out);
   const double* __restrict__ h = static_cast<const double*>(p.cond);
   const double* __restrict__ S = static_cast<const double*>(p.src);
+  const double* __restrict__ cap = static_cast<const double*>(p.cap);
   const Layout& L = p.L;
   const Box& b = p.box;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -127,6 +136,10 @@ __global__ __launch_bounds__(kCgThreads) void steady_apply_kernel(SteadyApplyPar
       if constexpr (RESID) {
         v = inc;
         if constexpr (SRC) v = add_source<double>(inc, S[c]);
+      } else if constexpr (SHIFT == 2) {
+        v = implicit_apply<true, double>(qc, inc, p.mu, cap[c]);
+      } else if constexpr (SHIFT == 1) {
+        v = implicit_apply<false, double>(qc, inc, p.mu, 0.0);
       } else {
         v = -inc;
       }
@@ -158,6 +171,8 @@ __device__ __forceinline__ void cg_rows(const Layout& L, const Box& b, Body body
   }
 }
 
+// XU: x += alpha p; RU: r -= alpha q with r . r (one of them at least)
+template <bool XU, bool RU>
 __global__ __launch_bounds__(kCgThreads) void steady_update_kernel(SteadyUpdateParams p, DD* partial) {
   __shared__ DD red[kCgWaves];
   if (cg_done(p.state)) return;
@@ -173,20 +188,26 @@ __global__ __launch_bounds__(kCgThreads) void steady_update_kernel(SteadyUpdateP
     for (int u = 0; u < kCgAhead; ++u) {
       const int64_t k = k0 + (int64_t)u * 64;
       if (k < hi) {
-        xv[u] = x[base + k];
-        dv[u] = d[base + k];
-        rv[u] = r[base + k];
-        qv[u] = q[base + k];
+        if constexpr (XU) {
+          xv[u] = x[base + k];
+          dv[u] = d[base + k];
+        }
+        if constexpr (RU) {
+          rv[u] = r[base + k];
+          qv[u] = q[base + k];
+        }
       }
     }
 #pragma unroll
     for (int u = 0; u < kCgAhead; ++u) {
       const int64_t k = k0 + (int64_t)u * 64;
       if (k < hi) {
-        x[base + k] = steady_axpy<double>(alpha, dv[u], xv[u]);
-        const double rn = steady_axpy<double>(-alpha, qv[u], rv[u]);
-        r[base + k] = rn;
-        dd_add(acc, rn * rn);
+        if constexpr (XU) x[base + k] = steady_axpy<double>(alpha, dv[u], xv[u]);
+        if constexpr (RU) {
+          const double rn = steady_axpy<double>(-alpha, qv[u], rv[u]);
+          r[base + k] = rn;
+          dd_add(acc, rn * rn);
+        }
       }
     }
   });
@@ -251,17 +272,19 @@ static void launch_final(DD* partial, int n, double* out, bool accumulate, const
   HIPK_CHECK(hipGetLastError());
 }
 
-template <bool COND, bool RESID, bool SRC>
+template <bool COND, bool RESID, bool SRC, int SHIFT = 0>
 static void launch_apply(const SteadyApplyParams& p, const ApplyGeom& g, int blocks, bool walls, DD* partial,
                          hipStream_t s) {
   const dim3 gr((unsigned)blocks), bl(kCgThreads);
-  if (walls) hipLaunchKernelGGL((steady_apply_kernel<COND, RESID, SRC, true>), gr, bl, 0, s, p, g, partial);
-  else hipLaunchKernelGGL((steady_apply_kernel<COND, RESID, SRC, false>), gr, bl, 0, s, p, g, partial);
+  if (walls) hipLaunchKernelGGL((steady_apply_kernel<COND, RESID, SRC, true, SHIFT>), gr, bl, 0, s, p, g, partial);
+  else hipLaunchKernelGGL((steady_apply_kernel<COND, RESID, SRC, false, SHIFT>), gr, bl, 0, s, p, g, partial);
 }
 
 void steady_apply(DType t, const SteadyApplyParams& p, void* scratch, double* out, bool accumulate, void* stream) {
   check_f64(t, "steady_apply");
   HEAT3D_CHECK(p.in && p.out && p.in != p.out && scratch, "steady_apply: two distinct fields and the partials");
+  HEAT3D_CHECK(!(p.shift && p.residual), "steady_apply: the residual form is not shifted");
+  HEAT3D_CHECK(p.shift || !p.cap, "steady_apply: a capacity goes with the shifted form only");
   check_box(p.L, p.box, 1, "steady_apply");
   const Box& b = p.box;
   DD* partial = static_cast<DD*>(scratch);
@@ -281,7 +304,12 @@ void steady_apply(DType t, const SteadyApplyParams& p, void* scratch, double* ou
     for (int a = 0; a < 3; ++a)
       for (int e = 0; e < 2; ++e) walls |= p.wall[a][e] >= b.lo[a] && p.wall[a][e] < b.hi[a];
     const bool src = p.residual && p.src;
-    if (p.cond) {
+    if (p.shift) {
+      if (p.cond && p.cap) launch_apply<true, false, false, 2>(p, g, blocks, walls, partial, S(stream));
+      else if (p.cond) launch_apply<true, false, false, 1>(p, g, blocks, walls, partial, S(stream));
+      else if (p.cap) launch_apply<false, false, false, 2>(p, g, blocks, walls, partial, S(stream));
+      else launch_apply<false, false, false, 1>(p, g, blocks, walls, partial, S(stream));
+    } else if (p.cond) {
       if (!p.residual) launch_apply<true, false, false>(p, g, blocks, walls, partial, S(stream));
       else if (src) launch_apply<true, true, true>(p, g, blocks, walls, partial, S(stream));
       else launch_apply<true, true, false>(p, g, blocks, walls, partial, S(stream));
@@ -302,12 +330,16 @@ static int row_blocks(const Box& b) {
 
 void steady_update(DType t, const SteadyUpdateParams& p, void* scratch, double* out, bool accumulate, void* stream) {
   check_f64(t, "steady_update");
-  HEAT3D_CHECK(p.x && p.p && p.r && p.q && scratch, "steady_update: four fields and the partials");
+  HEAT3D_CHECK((p.x != nullptr) == (p.p != nullptr) && (p.r != nullptr) == (p.q != nullptr) && (p.x || p.r) && scratch,
+               "steady_update: four fields (or x and p alone, or r and q alone) and the partials");
   check_box(p.L, p.box, 0, "steady_update");
   DD* partial = static_cast<DD*>(scratch);
   const int blocks = row_blocks(p.box);
   if (blocks > 0) {
-    hipLaunchKernelGGL(steady_update_kernel, dim3((unsigned)blocks), dim3(kCgThreads), 0, S(stream), p, partial);
+    const dim3 gr((unsigned)blocks), bl(kCgThreads);
+    if (p.x && p.r) hipLaunchKernelGGL((steady_update_kernel<true, true>), gr, bl, 0, S(stream), p, partial);
+    else if (p.r) hipLaunchKernelGGL((steady_update_kernel<false, true>), gr, bl, 0, S(stream), p, partial);
+    else hipLaunchKernelGGL((steady_update_kernel<true, false>), gr, bl, 0, S(stream), p, partial);
     HIPK_CHECK(hipGetLastError());
   }
   launch_final(partial, blocks, out, accumulate, p.state, S(stream));

@@ -113,9 +113,18 @@ struct SteadyApplyParams {
   double ambient = 0;
   bool residual = false;
   const SteadyState* state = nullptr;  // its done flag is honoured (nullptr: always runs)
+  // The shifted A-form of an implicit step (docs/ARCHITECTURE.md "Implicit
+  // steps"): out = (R + mu A) in, R = diag(1 / s) with s = `cap` in the same
+  // Layout (read at the centre of an updated point only), R = I when cap is
+  // nullptr; the dot product is in . out.  Not with the residual form.
+  bool shift = false;
+  double mu = 0;
+  const void* cap = nullptr;
 };
 
-// x += alpha p, r -= alpha q over a box, fused with r . r of the new r
+// x += alpha p, r -= alpha q over a box, fused with r . r of the new r.  With
+// x and p both nullptr only r is updated (alpha = 1: r -= q, the true residual
+// of an implicit step); with r and q both nullptr only x (the sum is 0).
 struct SteadyUpdateParams {
   void* x = nullptr;
   const void* p = nullptr;

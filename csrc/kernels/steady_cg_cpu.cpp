@@ -55,12 +55,16 @@ void reduce_rows(const Box& b, double* out, bool accumulate, Chunk chunk) {
   out[1] = total.lo;
 }
 
-template <bool COND, bool RESID>
+// SHIFT: 0 the plain forms, 1 the shifted A-form (implicit_apply), 2 with a capacity
+template <bool COND, bool RESID, int SHIFT = 0>
 DD apply_chunk(const SteadyApplyParams& p, int64_t r0, int64_t r1) {
+  static_assert(!(RESID && SHIFT), "the residual form is not shifted");
   const double* in = static_cast<const double*>(p.in);
   double* out = static_cast<double*>(p.out);
   const double* h = static_cast<const double*>(p.cond);
   const double* S = RESID ? static_cast<const double*>(p.src) : nullptr;
+  const double* cap = static_cast<const double*>(p.cap);
+  const double mu = p.mu;
   const Layout& L = p.L;
   const Box& b = p.box;
   const int64_t ey = b.extent(1), sx = L.sx, sy = L.sy;
@@ -87,6 +91,8 @@ DD apply_chunk(const SteadyApplyParams& p, int64_t r0, int64_t r1) {
         inc = steady_increment<double>(T, xm, xp, ym, yp, zm, zp, Dx, Dy, Dz);
       double v;
       if constexpr (RESID) v = S ? add_source<double>(inc, S[c]) : inc;
+      else if constexpr (SHIFT == 2) v = implicit_apply<true, double>(T, inc, mu, cap[c]);
+      else if constexpr (SHIFT == 1) v = implicit_apply<false, double>(T, inc, mu, 0.0);
       else v = -inc;
       out[c] = v;
       dd_add(acc, RESID ? v * v : T * v);
@@ -102,8 +108,14 @@ void steady_apply(DType t, const SteadyApplyParams& p, double* out, bool accumul
   HEAT3D_CHECK(p.in && p.out && p.in != p.out, "steady_apply: two distinct fields");
   check_reach(p.L, p.box, "steady_apply");
   if (p.state && p.state->done) return;
+  HEAT3D_CHECK(!(p.shift && p.residual), "steady_apply: the residual form is not shifted");
+  HEAT3D_CHECK(p.shift || !p.cap, "steady_apply: a capacity goes with the shifted form only");
   auto run = [&](auto chunk) { reduce_rows(p.box, out, accumulate, chunk); };
-  if (p.cond && p.residual) run([&](int64_t a, int64_t b) { return apply_chunk<true, true>(p, a, b); });
+  if (p.shift && p.cond && p.cap) run([&](int64_t a, int64_t b) { return apply_chunk<true, false, 2>(p, a, b); });
+  else if (p.shift && p.cond) run([&](int64_t a, int64_t b) { return apply_chunk<true, false, 1>(p, a, b); });
+  else if (p.shift && p.cap) run([&](int64_t a, int64_t b) { return apply_chunk<false, false, 2>(p, a, b); });
+  else if (p.shift) run([&](int64_t a, int64_t b) { return apply_chunk<false, false, 1>(p, a, b); });
+  else if (p.cond && p.residual) run([&](int64_t a, int64_t b) { return apply_chunk<true, true>(p, a, b); });
   else if (p.cond) run([&](int64_t a, int64_t b) { return apply_chunk<true, false>(p, a, b); });
   else if (p.residual) run([&](int64_t a, int64_t b) { return apply_chunk<false, true>(p, a, b); });
   else run([&](int64_t a, int64_t b) { return apply_chunk<false, false>(p, a, b); });
@@ -111,7 +123,8 @@ void steady_apply(DType t, const SteadyApplyParams& p, double* out, bool accumul
 
 void steady_update(DType t, const SteadyUpdateParams& p, double* out, bool accumulate) {
   check_f64(t, "steady_update");
-  HEAT3D_CHECK(p.x && p.p && p.r && p.q, "steady_update: four fields");
+  HEAT3D_CHECK((p.x != nullptr) == (p.p != nullptr) && (p.r != nullptr) == (p.q != nullptr) && (p.x || p.r),
+               "steady_update: four fields, or x and p alone, or r and q alone");
   check_inside(p.L, p.box, "steady_update");
   if (p.state && p.state->done) return;
   const double alpha = p.state ? p.state->alpha : p.alpha;
@@ -127,7 +140,8 @@ void steady_update(DType t, const SteadyUpdateParams& p, double* out, bool accum
     for (int64_t row = r0; row < r1; ++row) {
       const int64_t base = L.index(b.lo[0] + row / ey, b.lo[1] + row % ey, 0);
       for (int64_t k = b.lo[2]; k < b.hi[2]; ++k) {
-        x[base + k] = steady_axpy<double>(alpha, d[base + k], x[base + k]);
+        if (x) x[base + k] = steady_axpy<double>(alpha, d[base + k], x[base + k]);
+        if (!r) continue;
         const double rn = steady_axpy<double>(-alpha, q[base + k], r[base + k]);
         r[base + k] = rn;
         dd_add(acc, rn * rn);

@@ -177,8 +177,12 @@ SteadyApplyParams steady_aparams(int64_t in_ptr, int64_t out_ptr, const std::arr
                                  const std::array<int64_t, 3>& g, const std::array<int64_t, 6>& box,
                                  const std::array<double, 3>& D, int64_t src_ptr, int64_t cond_ptr,
                                  const std::array<int64_t, 6>& wall, const std::array<int, 6>& kind,
-                                 const std::array<double, 6>& beta, double ambient, bool residual) {
+                                 const std::array<double, 6>& beta, double ambient, bool residual, bool shift,
+                                 double mu, int64_t cap_ptr) {
   SteadyApplyParams p;
+  p.shift = shift;
+  p.mu = mu;
+  p.cap = reinterpret_cast<const void*>(cap_ptr);
   p.in = reinterpret_cast<const void*>(in_ptr);
   p.out = reinterpret_cast<void*>(out_ptr);
   p.src = reinterpret_cast<const void*>(src_ptr);
@@ -761,8 +765,10 @@ PYBIND11_MODULE(_heat3d, m) {
   hk.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
                             std::array<int64_t, 6> box, std::array<double, 3> D, int64_t src_ptr, int64_t cond_ptr,
                             std::array<int64_t, 6> wall, std::array<int, 6> kind, std::array<double, 6> beta,
-                            double ambient, bool residual, int64_t scratch_ptr, int64_t dot_ptr, int64_t stream) {
-    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta, ambient, residual);
+                            double ambient, bool residual, bool shift, double mu, int64_t cap_ptr,
+                            int64_t scratch_ptr, int64_t dot_ptr, int64_t stream) {
+    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta,
+                                               ambient, residual, shift, mu, cap_ptr);
     hip::steady_apply(DType::F64, p, reinterpret_cast<void*>(scratch_ptr), reinterpret_cast<double*>(dot_ptr), false,
                       reinterpret_cast<void*>(stream));
   });
@@ -892,8 +898,9 @@ PYBIND11_MODULE(_heat3d, m) {
   ck.def("steady_apply", [](int64_t in_ptr, int64_t out_ptr, std::array<int64_t, 3> n, std::array<int64_t, 3> g,
                             std::array<int64_t, 6> box, std::array<double, 3> D, int64_t src_ptr, int64_t cond_ptr,
                             std::array<int64_t, 6> wall, std::array<int, 6> kind, std::array<double, 6> beta,
-                            double ambient, bool residual, int64_t dot_ptr) {
-    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta, ambient, residual);
+                            double ambient, bool residual, bool shift, double mu, int64_t cap_ptr, int64_t dot_ptr) {
+    const SteadyApplyParams p = steady_aparams(in_ptr, out_ptr, n, g, box, D, src_ptr, cond_ptr, wall, kind, beta,
+                                               ambient, residual, shift, mu, cap_ptr);
     py::gil_scoped_release nogil;
     cpu::steady_apply(DType::F64, p, reinterpret_cast<double*>(dot_ptr), false);
   });
@@ -1053,6 +1060,27 @@ PYBIND11_MODULE(_heat3d, m) {
         d["status"] = status[r.status >= 0 && r.status < 4 ? r.status : 0];
         return d;
       }, py::arg("tol") = 1e-8, py::arg("max_iter") = 0)
+      .def("step_implicit", [](Solver& s, int64_t steps, double m, double theta, double tol, int64_t max_iter) {
+        ImplicitResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = s.step_implicit(steps, m, theta, tol, max_iter);
+        }
+        py::dict d;
+        d["converged"] = r.converged;
+        d["steps_done"] = r.steps_done;
+        d["time_advanced"] = r.time_advanced;
+        d["iterations"] = r.iterations;
+        d["step_iterations"] = r.step_iterations;
+        d["residual"] = r.residual;
+        d["true_residual"] = r.true_residual;
+        d["r0_norm"] = r.r0_norm;
+        d["seconds"] = r.seconds;
+        d["restarts"] = r.restarts;
+        static const char* status[] = {"running", "converged", "max_iter", "breakdown"};
+        d["status"] = status[r.status >= 0 && r.status < 4 ? r.status : 0];
+        return d;
+      }, py::arg("steps"), py::arg("m"), py::arg("theta") = 1.0, py::arg("tol") = 1e-8, py::arg("max_iter") = 0)
       .def("gather_global", [](Solver& s) -> py::object {
         std::vector<double> v;
         bool root;

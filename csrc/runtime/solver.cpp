@@ -484,6 +484,7 @@ Solver::~Solver() {
     if (l.cap) be_->release(l.cap);
     if (l.steady_r) be_->release(l.steady_r);
     if (l.steady_q) be_->release(l.steady_q);
+    if (l.steady_d) be_->release(l.steady_d);
     for (auto& io : l.faces) {
       be_->release(io.sendbuf);
       be_->release(io.recvbuf);

@@ -78,6 +78,21 @@ struct SteadyResult {
   int status = 0;              // SteadyStatus of the last recurrence
 };
 
+// Solver::step_implicit's report
+struct ImplicitResult {
+  bool converged = false;       // every step taken ended with its recomputed residual within tol
+  int64_t steps_done = 0;       // steps whose result is in the field
+  double time_advanced = 0.0;   // steps_done * m, in explicit time steps
+  int64_t iterations = 0;       // CG iterations of all steps
+  std::vector<int64_t> step_iterations;  // ... of each step taken
+  double residual = 0.0;        // of the last step, as SteadyResult's
+  double true_residual = 0.0;
+  double r0_norm = 0.0;         // ||r(T)|| at the start of the last step
+  double seconds = 0.0;
+  int restarts = 0;             // restarts from the true residual, all steps
+  int status = 0;               // SteadyStatus of the last step's last recurrence
+};
+
 struct HostState {
   double norm, eps, last_residual, error_sum, error_count;
   int64_t iter, conv_iter;
@@ -243,6 +258,22 @@ class Solver {
   // --compat, and not with every face insulated (UsageError).
   SteadyResult solve_steady(double tol, int64_t max_iter = 0);
 
+  // Implicit time steps (docs/ARCHITECTURE.md "Implicit steps"): `steps` steps
+  // of length m > 0 explicit time steps each, theta in [0.5, 1] (1: backward
+  // Euler, 0.5: Crank-Nicolson).  One step solves R (T' - T) = m [theta r(T') +
+  // (1 - theta) r(T)], R = diag(rc) (the heat capacity, honoured here; I
+  // without one), in increment form (R + theta m A) d = r(T), T' = fma(m, d, T),
+  // by the conjugate gradients of solve_steady from d = 0 until ||r_k|| <= tol
+  // ||r(T)|| or max_iter iterations per step (<= 0: 10 (Nx + Ny + Nz)).  The
+  // system is positive definite in every mode, every face insulated included.
+  // A step whose r(T) is zero leaves the field's bits alone; a step whose
+  // r . r is not finite leaves the field as it was before that step and ends
+  // the call (status breakdown); a step that stops at max_iter is applied and
+  // ends the call.  Afterwards the time-step state restarts at iteration 0, as
+  // after set_field.  Same call, same bits; decompositions agree to the
+  // tolerance.  Synchronises; collective.  fp64 only, not with --compat.
+  ImplicitResult step_implicit(int64_t steps, double m, double theta, double tol, int64_t max_iter = 0);
+
   // Field access.  gather_global fills `out` (N0*N1*N2 values as double,
   // z fastest) on the root process only; returns false elsewhere.
   bool gather_global(std::vector<double>* out);
@@ -352,6 +383,7 @@ class Solver {
     void* cap = nullptr;     // s = dtype(1 / rc) in layout L, allocated by set_capacity
     void* steady_r = nullptr;  // solve_steady: residual and A p, in layout L, allocated on first use
     void* steady_q = nullptr;
+    void* steady_d = nullptr;  // step_implicit: the increment d, in layout L, allocated on first use
     Box owned, interior;
     std::vector<Box> shell;
     std::vector<FaceIO> faces;
@@ -580,6 +612,27 @@ class Solver {
   SteadyState* cg_host_ = nullptr;
   SteadyApplyParams steady_params(const Local& l) const;  // box, walls, D, Ch, S of a subdomain
   void steady_allreduce(double* pair);
+  // r, q (and d: step_implicit) of every subdomain and the device scalars, on first use
+  void steady_workspace(bool with_d);
+  // The CG loop solve_steady and step_implicit share: from the unknown x_of(l)
+  // with the direction in buffer pb.  true_residual(first) leaves b - A x in
+  // steady_r and its r . r (all-reduced) in cg_state_->rrn, whatever the flag
+  // says; shape adds what the A-form needs on top of steady_params.  Scalar
+  // steps, the poll every kPoll iterations, the done flag and at most
+  // kMaxRestarts restarts from the true residual are in here; nothing of the
+  // time-step state is touched.
+  struct CgOutcome {
+    SteadyState hs;
+    double true_rr = 0.0;
+    bool finite = true;
+    int restarts = 0;
+  };
+  CgOutcome cg_solve(double tol, int64_t max_iter, int pb, const std::function<void*(Local&)>& x_of,
+                     const std::function<void(SteadyApplyParams&, const Local&)>& shape,
+                     const std::function<void(bool)>& true_residual);
+  // the current buffer becomes the state of iteration 0 (walls refreshed,
+  // ghosts at full depth; every buffer of the rotation holds it when `all`)
+  void steady_publish(int xb, bool all);
   DeviceState* hstate_ = nullptr;   // pinned host mirror
   int64_t issued_ = 0;              // iterations enqueued so far (absolute index)
   int cur_ = 0;               // buffer holding T^{issued_}

@@ -112,6 +112,19 @@ class HeatEquation3D:
         T = v[0][:, None, None] * v[1][None, :, None] * v[2][None, None, :]
         return T, float(1.0 - float(s) * 4.0 * lam)
 
+    def implicit_factor(self, m_vec: Sequence[int], m: float, theta: float, s: float = 1.0) -> float:
+        """Exact factor by which one implicit step (``HeatSolver.step_implicit``)
+        of length ``m`` explicit steps with ``theta`` multiplies the mode
+        ``dirichlet_mode(m_vec)`` in a body with the uniform capacity factor
+        ``s`` = 1 / rc: (1 - (1 - theta) m s lam) / (1 + theta m s lam) with
+        lam = 4 sum_a D_a sin^2(pi m_a / (2 (N_a - 1)))."""
+        lam = 0.0
+        for a in range(3):
+            lam += self.D[a] * np.sin(np.pi * m_vec[a] / (2.0 * (self.n[a] - 1))) ** 2
+        lam *= 4.0
+        msl = float(m) * float(s) * lam
+        return float((1.0 - (1.0 - float(theta)) * msl) / (1.0 + float(theta) * msl))
+
     def layered_steady(self, c: np.ndarray) -> np.ndarray:
         """Exact steady state of the discrete scheme for a conductivity that
         varies in y only, between the walls T(y=0) = 0 and T(y=1) = 1: a
@@ -445,8 +458,8 @@ class HeatSolver:
         (``conductivity_sweeps`` and ``wall_source_sweeps`` mean nothing) unless a
         conductivity is set too and ``capacity_sweeps=True`` asks for the K-step
         sweeps of the tc kernels (same bits; without a conductivity that flag
-        does nothing), the stored heat of ``heat_balance()`` is weighted with rc, and the steady
-        state (``solve_steady``) is the one without a capacity.  A body with
+        does nothing), the stored heat of ``heat_balance()`` is weighted with rc, the steady
+        state (``solve_steady``) is the one without a capacity, and ``step_implicit`` honours it.  A body with
         rc == 1 everywhere agrees with one without a capacity to rounding, not
         bitwise.  Keeps the field, restarts the iteration count and the
         convergence state at 0.  Collective."""
@@ -532,6 +545,36 @@ class HeatSolver:
         singular: each a ``UsageError``.  Synchronises; collective."""
         self._ensure()
         return dict(self._s.solve_steady(float(tol), 0 if max_iter is None else int(max_iter)))
+
+    def step_implicit(self, steps: int, m: float, theta: float = 1.0, tol: float = 1e-8,
+                      max_iter: Optional[int] = None) -> Dict:
+        """Implicit time steps: ``steps`` steps, each ``m`` > 0 explicit time steps
+        long, with ``theta`` in [0.5, 1] (1 backward Euler, 0.5 Crank-Nicolson).
+        One step solves ``R (T' - T) = m [theta r(T') + (1 - theta) r(T)]`` with
+        ``r(T) = G(T) - T`` the explicit increment of the current mode without
+        the capacity and ``R = diag(rc)`` (the heat capacity is honoured here),
+        as ``(R + theta m A) d = r(T)``, ``T' = T + m d``, by the conjugate
+        gradients of ``solve_steady`` from ``d = 0`` until the residual's 2-norm
+        is ``tol`` times ``||r(T)||`` or ``max_iter`` iterations per step
+        (default ``10 (Nx + Ny + Nz)``).  Every mode of ``solve_steady`` works,
+        and so do a capacity and a body with every face insulated.  The result
+        becomes the current field and the time-step state restarts at
+        iteration 0, as after ``set_field``.
+
+        Returns ``steps_done``, ``time_advanced`` (``steps_done * m``),
+        ``iterations`` (total) and ``step_iterations`` (per step), ``residual``,
+        ``true_residual`` and ``r0_norm`` of the last step, ``restarts``,
+        ``status``, ``seconds`` and ``converged`` (every step's recomputed
+        residual within ``tol``).  A step whose ``r(T)`` is zero takes no
+        iteration and leaves the field's bits alone.  A non-finite ``r . r``
+        gives ``"breakdown"``: the field stays as it was before that step and
+        the call returns.  A step that stops at ``max_iter`` is applied and ends
+        the call.  Same call, same bits; decompositions agree to the tolerance.
+        fp64 only; not with ``compat``; ``m``, ``theta``, ``tol`` or ``steps``
+        out of range: each a ``UsageError``.  Synchronises; collective."""
+        self._ensure()
+        return dict(self._s.step_implicit(int(steps), float(m), float(theta), float(tol),
+                                          0 if max_iter is None else int(max_iter)))
 
     def write_tecplot(self, path: str = "output/out.dat", layout: str = "auto") -> None:
         self._s.write_tecplot(path, layout)

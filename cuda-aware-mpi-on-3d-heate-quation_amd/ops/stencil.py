@@ -446,7 +446,8 @@ def steady_apply(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Op
                  wall: Optional[Sequence[int]] = None, kind: Optional[Sequence[int]] = None,
                  beta: Optional[Sequence[float]] = None, ambient: float = 0.0,
                  source: Optional[PaddedField] = None, cond: Optional[PaddedField] = None,
-                 residual: bool = False) -> Tuple[float, float]:
+                 residual: bool = False, shift: Optional[float] = None,
+                 cap: Optional[PaddedField] = None) -> Tuple[float, float]:
     """The steady solve's operator on ``box`` (default: all owned points), fp64:
     ``dst = A src`` with the dot product ``src . dst``, or (``residual``)
     ``dst = b - A src`` with ``dst . dst``, returned as the double-double pair
@@ -459,17 +460,26 @@ def steady_apply(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Op
     Across a wall the neighbour is: Dirichlet 0 (residual: the stored vertex),
     insulated the centre, convective ``fma(beta, 0 - c, c)`` (residual: towards
     ``ambient``).  ``cond``: Ch = 0.5 c; ``source``: S = dt q (residual only).
+    ``shift`` = mu: the shifted operator of an implicit step instead,
+    ``dst = (R + mu A) src`` with ``src . dst``, R = diag(1 / s) with ``cap`` = s
+    (read at the centre of an updated point only), R = I without ``cap``; not
+    with ``residual``, and ``cap`` only with ``shift``.
     GPU tensors run steady_cg.hip on torch's current stream, CPU tensors the
     definition; the field written is bitwise the same."""
     ext = native()
-    f0 = _steady_check(src, dst)
+    f0 = _steady_check(src, dst) if cap is None else _steady_check(src, dst, cap)
+    if shift is not None and residual:
+        raise ValueError("steady_apply: the residual form is not shifted")
+    if cap is not None and shift is None:
+        raise ValueError("steady_apply: cap goes with shift only")
     n = f0.n
     b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
     w = list(wall) if wall is not None else [0, n[0] - 1, 0, n[1] - 1, 0, n[2] - 1]
     kd = [int(v) for v in kind] if kind is not None else [0] * 6
     bt = [float(v) for v in beta] if beta is not None else [0.0] * 6
     args = (src.data_ptr(), dst.data_ptr(), list(n), [f0.gx, f0.gy, f0.gz], b, [float(v) for v in D],
-            _source_ptr(src, source), _cond_ptr(src, cond), w, kd, bt, float(ambient), bool(residual))
+            _source_ptr(src, source), _cond_ptr(src, cond), w, kd, bt, float(ambient), bool(residual),
+            shift is not None, 0.0 if shift is None else float(shift), 0 if cap is None else cap.data_ptr())
 
     def launch(dot, scratch, stream):
         if scratch is None:
@@ -480,15 +490,21 @@ def steady_apply(src: PaddedField, dst: PaddedField, D: Sequence[float], box: Op
     return _steady_dot(f0, launch)
 
 
-def steady_update(x: PaddedField, p: PaddedField, r: PaddedField, q: PaddedField, alpha: float,
-                  box: Optional[Sequence[int]] = None) -> Tuple[float, float]:
+def steady_update(x: Optional[PaddedField], p: Optional[PaddedField], r: Optional[PaddedField],
+                  q: Optional[PaddedField], alpha: float, box: Optional[Sequence[int]] = None) -> Tuple[float, float]:
     """``x += alpha p``, ``r -= alpha q`` on ``box`` (one fused multiply-add
-    each) and the new ``r . r`` as the double-double pair (hi, lo)."""
+    each) and the new ``r . r`` as the double-double pair (hi, lo).  ``x`` and
+    ``p`` both None: only ``r`` is updated (``alpha`` = 1: ``r -= q``, the true
+    residual of an implicit step); ``r`` and ``q`` both None: only ``x``
+    (``T' = fma(m, d, T)``), and the pair is (0, 0)."""
     ext = native()
-    f0 = _steady_check(x, p, r, q)
+    if (x is None) != (p is None) or (r is None) != (q is None) or (x is None and r is None):
+        raise ValueError("steady_update: four fields, or x and p alone, or r and q alone")
+    f0 = _steady_check(*[f for f in (x, p, r, q) if f is not None])
     n = f0.n
     b = list(box) if box is not None else [0, n[0], 0, n[1], 0, n[2]]
-    args = (x.data_ptr(), p.data_ptr(), r.data_ptr(), q.data_ptr(), list(n), [f0.gx, f0.gy, f0.gz], b, float(alpha))
+    args = tuple(0 if f is None else f.data_ptr() for f in (x, p, r, q)) + (
+        list(n), [f0.gx, f0.gy, f0.gz], b, float(alpha))
 
     def launch(dot, scratch, stream):
         if scratch is None:
